@@ -26,7 +26,19 @@ taken from the next loop in that order, and `timed_loop` says which.
 `roofline.kernel_ms` times the headline loop's own launch (back-to-back
 RolloutRunner.run() calls bracketed by HIP events on their stream).
 
-    python bench.py [--gpus N --steps K --warmup W --batch B]
+A plain run does only what `value` needs: set-up, the warm-up, the headline
+loop's timed regions, the result line. The other loops, `roofline`,
+`secondary_configs`, `phase_roofline` and `cpu_baseline` are measured (and
+their keys are in the line) under `--full` only. `--dump-outputs DIR` writes
+the state the headline loop computed in its last timed step (the State a
+caller of that loop receives: pos, rot, vel, ang, obs, reward, done, steps,
+truncation, metrics) as DIR/<name>.npy, float32, at most 64 MB in all (a
+seeded sample of the envs above that; rank 0's shard when N > 1). The same
+arguments give the same inputs and the same number of steps before that state
+on every run.
+
+    python bench.py [--gpus N --steps K --warmup W --batch B] [--full]
+                    [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N   (one rank per GPU)
 
 Multi-GPU: rank r owns the global envs [r*B, (r+1)*B) (weak scaling). Reset
@@ -73,8 +85,11 @@ REF_PUBLISHED = 895723.0
 # GRAPH_MAX steps (one replay, one action draw), else gcd(steps, GRAPH_STEPS)
 GRAPH_STEPS = 50
 GRAPH_MAX = 200
-# least warm-up of each replayed loop, seconds of its own work
-WARM_S = 0.02
+# least warm-up of each replayed loop, seconds of its own work (0.25 s: a
+# plain run has no earlier loop's load behind it when the headline loop
+# starts; at 0.02 s its 20-step value read ~0.5 % lower than with the other
+# loops run first, at 0.25 s ~0.2 %, both inside the 1.3 % run-to-run spread)
+WARM_S = 0.25
 # the timed loops, in order: the eager Python loop, StepGraph replays,
 # RolloutGraph replays, RolloutRunner (direct rollout launches)
 KINDS = ('eager', 'step', 'rollout', 'direct')
@@ -505,6 +520,46 @@ def clone_state(st):
                     reward=st.reward.clone(), done=st.done.clone(), info=info)
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def state_arrays(st, metric_keys):
+  """State `st` as host float32 arrays: pos / rot / vel / ang (B, N, 3 | 4),
+  obs, reward, done, steps, truncation, metrics (B, M; columns
+  `metric_keys`)."""
+  from brax_amd.base import packed_buffer
+  qb = packed_buffer(st.qp)
+  if qb is not None:
+    qp = {'pos': qb[..., 0:3], 'rot': qb[..., 3:7], 'vel': qb[..., 7:10], 'ang': qb[..., 10:13]}
+  else:
+    qp = {'pos': st.qp.pos, 'rot': st.qp.rot, 'vel': st.qp.vel, 'ang': st.qp.ang}
+  arrays = dict(qp, obs=st.obs, reward=st.reward, done=st.done)
+  for k in ('steps', 'truncation'):
+    if st.info.get(k) is not None:
+      arrays[k] = st.info[k]
+  cols = [st.metrics[k] for k in metric_keys if k in st.metrics]
+  if cols:
+    arrays['metrics'] = torch.stack([c.float() for c in cols], dim=1)
+  return {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+
+
+def dump_outputs(path, arrays):
+  """Writes `state_arrays`' arrays as `path`/<name>.npy. Above DUMP_MAX_BYTES
+  in all, a fixed seeded sample of the envs (the same rows of every array;
+  their ids in env_ids.npy, float64)."""
+  B = arrays['obs'].shape[0]
+  per_env = sum(a.size // B for a in arrays.values()) * 4 + 8
+  keep = DUMP_MAX_BYTES // per_env
+  os.makedirs(path, exist_ok=True)
+  if B > keep:
+    ids = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+    arrays = {k: a[ids] for k, a in arrays.items()}
+    arrays['env_ids'] = ids.astype(np.float64)
+  for k, a in arrays.items():
+    np.save(os.path.join(path, k + '.npy'), np.ascontiguousarray(a))
+  return sorted(arrays)
+
+
 def runner_train(env, state, k, n=20):
   """Per-step duration of the headline loop's own launch: `n` back-to-back
   `RolloutRunner.run()` calls of `k` steps (one `bx_env_rollout_random`
@@ -575,12 +630,18 @@ def main():
   ap.add_argument('--steps', type=int, default=1000)
   ap.add_argument('--warmup', type=int, default=50)
   ap.add_argument('--batch', type=int, default=4096)
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='also time the eager / graph / rollout loops and measure the roofline, '
+                       'the secondary configs, the phase kernels and the CPU baseline')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write the state of the last timed step as DIR/<name>.npy')
+  ap.add_argument('--no-cpu-baseline', action='store_true',
+                  help='with --full: skip the CPU baseline leg')
   ap.add_argument('--no-phases', action='store_true',
-                  help='skip the standalone SoA phase-kernel roofline leg')
+                  help='with --full: skip the standalone SoA phase-kernel roofline leg')
   ap.add_argument('--phase-envs', type=int, default=1 << 20)
   ap.add_argument('--no-secondary', action='store_true',
-                  help='skip the Humanoid / Ant Mountain legs')
+                  help='with --full: skip the Humanoid / Ant Mountain legs')
   ap.add_argument('--repeats', type=int, default=5,
                   help='timed regions of the direct (headline) loop; value = their median')
   ap.add_argument('--generic', action='store_true',
@@ -639,32 +700,46 @@ def main():
 
   for k in range(args.warmup):
     state = one_step(state, k)
-  # no collector pause inside a timed region; collected BEFORE the warm-up
-  # work: a collection between the warm-up and t0 idles the GPU for
-  # milliseconds, its clock drops, and a short timed region (the driver's
-  # 20 steps are ONE rollout launch) runs on the ramp
-  gc.collect()
-  gc.disable()
-  # the step kernel alone (its launch train also brings the clocks up before
-  # the timed loops)
-  kern_ms = single_ms = kernel_train(env, state, act)
-  if exchange is not None:
-    exchange.reset()
-  torch.cuda.synchronize()
-  if dist is not None:
-    dist.barrier()
-  torch.cuda.synchronize()
-  t0 = time.perf_counter()
-  for k in range(args.steps):
-    state = one_step(state, args.warmup + k)
-  torch.cuda.synchronize()
-  if dist is not None:  # (one rank: the synchronisation above is the bracket)
-    dist.barrier()
+  metric_keys = tuple(env.unwrapped.metric_keys)
+  snaps = {}  # per loop: the host arrays of its last timed step (--dump-outputs)
+
+  def eager_region(st):
+    """The eager Python loop's timed region: (state, elapsed, collectives)."""
+    if exchange is not None:
+      exchange.reset()
     torch.cuda.synchronize()
-  elapsed = time.perf_counter() - t0
-  gc.enable()
-  eager_elapsed = elapsed
-  eager_collectives = exchange.flushes if exchange is not None else 0
+    if dist is not None:
+      dist.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for k in range(args.steps):
+      st = one_step(st, args.warmup + k)
+    torch.cuda.synchronize()
+    if dist is not None:  # (one rank: the synchronisation above is the bracket)
+      dist.barrier()
+      torch.cuda.synchronize()
+    el = time.perf_counter() - t0
+    if args.dump_outputs:
+      snaps['eager'] = state_arrays(st, metric_keys)
+    return st, el, exchange.flushes if exchange is not None else 0
+
+  loops = {}
+  kern_ms = single_ms = None
+  k0 = args.warmup
+  if args.full:
+    # no collector pause inside a timed region; collected BEFORE the warm-up
+    # work: a collection between the warm-up and t0 idles the GPU for
+    # milliseconds, its clock drops, and a short timed region (the driver's
+    # 20 steps are ONE rollout launch) runs on the ramp
+    gc.collect()
+    gc.disable()
+    # the step kernel alone (its launch train also brings the clocks up before
+    # the timed loops)
+    kern_ms = single_ms = kernel_train(env, state, act)
+    state, eager_elapsed, eager_collectives = eager_region(state)
+    gc.enable()
+    loops['eager'] = ([eager_elapsed], eager_collectives, None)
+    k0 += args.steps
   # the same loop replayed from hipGraphs, the actions continuing the eager
   # loop's (step, global env id) stream: (1) StepGraph: K steps per graph
   # launch (one draw of the K action slabs, then K x (Env.step + the episodic
@@ -675,14 +750,17 @@ def main():
   from brax_amd.envs.graph import StepGraph
   from brax_amd.envs.rollout import RolloutGraph, RolloutRunner
 
-  def timed_replays(g, advance_hook, repeats=1):
+  def timed_replays(g, advance_hook, repeats=1, twin=None):
     """Warm replays, then `repeats` timed regions of args.steps // K replays
     each (barrier + sync on both sides of every region); the elapsed wall
-    time of each region, the collectives inside each and the replays run
-    untimed + timed. The warm-up is max(warmup // K, 2) replays, extended
+    time of each region, the collectives inside each and the replays of `g`
+    run untimed + timed. The warm-up is max(warmup // K, 2) replays, extended
     to WARM_S of the loop's own work: the GPU's clock ramps over ~10 ms of
     load (a 20-step rollout launch runs 506 us cold, 471 us warm in one
-    rocprof trace), so the timed region starts at the steady state."""
+    rocprof trace), so the timed region starts at the steady state. With
+    `twin` (a second loop built like `g`) the extension, whose length depends
+    on the clock, replays the twin: `g` then runs the same number of steps on
+    every run, and so ends in the same state."""
     fire = g.run if isinstance(g, RolloutRunner) else g.replay
     gc.collect()  # before the warm replays (see the eager loop)
     gc.disable()
@@ -693,9 +771,13 @@ def main():
     torch.cuda.synchronize()
     per = (time.perf_counter() - t_w) / n_warm
     extra = max(0, math.ceil((WARM_S - per * n_warm) / max(per, 1e-6)))
+    if twin is None:
+      n_warm += extra
+      twin_fire = fire
+    else:
+      twin_fire = twin.run if isinstance(twin, RolloutRunner) else twin.replay
     for _ in range(extra):
-      fire()
-    n_warm += extra
+      twin_fire()
     els, cols = [], []
     for _ in range(repeats):
       if exchange is not None:
@@ -743,75 +825,115 @@ def main():
 
   adv = None if exchange is None else exchange.advance
   # per loop: the timed regions' elapsed times (the direct loop's timed
-  # region runs `--repeats` times; the others once), collectives, error
+  # region runs `--repeats` times; the others once), collectives, error.
+  # A plain run times the headline loop alone: the direct loop, and the next
+  # of rollout, step, eager only when the one before could not run
   R = max(int(args.repeats), 1)
-  loops = {'eager': ([eager_elapsed], eager_collectives, None)}
-  k0 = args.warmup + args.steps
-  for kind in KINDS[1:]:
+  direct_draw = None
+  for kind in (KINDS[1:] if args.full else ('direct', 'rollout', 'step')):
     g, err = build(kind, state, k0)
-    if agreed(g is not None):
-      els, col, n_run = timed_replays(g, adv, R if kind == 'direct' else 1)
+    # a loop that can be the headline gets a twin for the clock-dependent
+    # part of its warm-up (see timed_replays)
+    twin = None
+    if g is not None and (kind == 'direct' or not args.full):
+      twin, err = build(kind, state, k0)
+    if agreed(g is not None and err is None):
+      els, col, n_run = timed_replays(g, adv, R if kind == 'direct' else 1, twin)
       loops[kind] = (els, col, None)
+      if kind == 'direct':
+        direct_draw = g.draw
       k0 += (n_run + args.steps // K) * K
       state = clone_state(g.state() if kind == 'direct' else  # pylint: disable=protected-access
                           g._res[0] if kind == 'rollout' else g._out)
+      if args.dump_outputs:
+        snaps[kind] = state_arrays(g.state() if kind == 'direct' else  # pylint: disable=protected-access
+                                   g._res[0] if kind == 'rollout' else g._out, metric_keys)
     else:
       loops[kind] = (None, 0, err)
-    del g
+    del g, twin
+    if not args.full and loops[kind][0] is not None:
+      break
+  if not any(v[0] is not None for v in loops.values()):
+    gc.collect()
+    gc.disable()
+    state, eager_elapsed, eager_collectives = eager_region(state)
+    gc.enable()
+    loops['eager'] = ([eager_elapsed], eager_collectives, None)
+  ran = [k for k in KINDS if k in loops]
   if dist is not None:
     # each region's time is its slowest rank's
     t = torch.tensor([loops[k][0][i] if loops[k][0] is not None else -1.0
-                      for k in KINDS for i in range(R if k == 'direct' else 1)],
+                      for k in ran for i in range(R if k == 'direct' else 1)],
                      dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     v = t.tolist()
-    for k in KINDS:
+    for k in ran:
       n = R if k == 'direct' else 1
       part, v = v[:n], v[n:]
       loops[k] = ((part if part[0] >= 0 else None),) + loops[k][1:]
   # a loop's time: the median of its timed regions (one region but the
   # direct loop's; its region is one K-step launch at the driver's 20 steps,
   # so a single launch or clock hiccup would move a lone sample by several %)
-  samples = {k: loops[k][0] for k in KINDS}
+  samples = {k: loops[k][0] for k in ran}
   loops = {k: ((float(np.median(e)) if e is not None else None),) + loops[k][1:]
-           for k, e in ((k, loops[k][0]) for k in KINDS)}
+           for k, e in ((k, loops[k][0]) for k in ran)}
   # the headline is the direct loop by design; another loop only if it failed
-  best = next(k for k in ('direct', 'rollout', 'step', 'eager') if loops[k][0] is not None)
+  best = next(k for k in ('direct', 'rollout', 'step', 'eager')
+              if k in loops and loops[k][0] is not None)
   elapsed, collectives = loops[best][0], loops[best][1]
-  eager_elapsed = loops['eager'][0]
 
   total = B * world * args.steps
   value = total / elapsed
   if rank != 0:
     dist.destroy_process_group()
     return
-  # the dominant kernel of the timed loop: the K-step rollout kernel (one
-  # launch = K x B env-steps) or the single-step kernel (one launch = B
-  # env-steps); achieved = algorithmic flops (bytes) per launch / launch time
-  direct_draw = None
-  if best in ('rollout', 'direct'):
-    kname, spl = ANT_ROLLOUT_KERNEL, K
-    ms_step, direct_draw = runner_train(env, state, K)
-    kern_ms = ms_step * K
-    kern_src = (f'HIP events over 20 back-to-back {K}-step RolloutRunner.run() launches '
-                f'({"bx_env_rollout_random: actions drawn inside the launch" if direct_draw else "bx_uniform_slabs + bx_env_rollout_packed"}) '
-                'on the launch stream (runner_train): the headline loop\'s own launch')
-  else:
-    kname, spl = ANT_KERNEL, 1
-    kern_src = ('HIP events over 200 back-to-back bx_env_step_packed launches on the launch '
-                'stream (kernel_train)')
-  bytes_per_launch = ANT_BYTES_PER_ENV_STEP * B * spl
-  flops_per_launch = ANT_FLOPS_PER_ENV_STEP * B * spl
-  tflops = flops_per_launch / (kern_ms * 1e-3) / 1e12
-  achieved_gbs = bytes_per_launch / (kern_ms * 1e-3) / 1e9
-  # PMC traffic of THIS kernel instantiation (Ant: 16 lanes, SINGLE mode,
-  # features F_G1 | F_JH, gather width 4), per env-step x the launch's steps
-  tr = _traffic()
-  k = ((tr or {}).get('kernels') or {}).get(kname)
-  traffic = (k['hbm_bytes_per_launch'] / k.get('steps_per_launch', 1) * spl
-             if k and k.get('batch') == B else None)
-  rp = _rocprof_avg(kname, spl)
-  sq = (rp or {}).get('sq') or {}
+  if args.dump_outputs:
+    dumped = dump_outputs(args.dump_outputs, snaps[best])
+  if args.full:
+    # the dominant kernel of the timed loop: the K-step rollout kernel (one
+    # launch = K x B env-steps) or the single-step kernel (one launch = B
+    # env-steps); achieved = algorithmic flops (bytes) per launch / launch time
+    if best in ('rollout', 'direct'):
+      kname, spl = ANT_ROLLOUT_KERNEL, K
+      ms_step, direct_draw = runner_train(env, state, K)
+      kern_ms = ms_step * K
+      kern_src = (f'HIP events over 20 back-to-back {K}-step RolloutRunner.run() launches '
+                  f'({"bx_env_rollout_random: actions drawn inside the launch" if direct_draw else "bx_uniform_slabs + bx_env_rollout_packed"}) '
+                  'on the launch stream (runner_train): the headline loop\'s own launch')
+    else:
+      kname, spl = ANT_KERNEL, 1
+      kern_src = ('HIP events over 200 back-to-back bx_env_step_packed launches on the launch '
+                  'stream (kernel_train)')
+    bytes_per_launch = ANT_BYTES_PER_ENV_STEP * B * spl
+    flops_per_launch = ANT_FLOPS_PER_ENV_STEP * B * spl
+    tflops = flops_per_launch / (kern_ms * 1e-3) / 1e12
+    achieved_gbs = bytes_per_launch / (kern_ms * 1e-3) / 1e9
+    # PMC traffic of THIS kernel instantiation (Ant: 16 lanes, SINGLE mode,
+    # features F_G1 | F_JH, gather width 4), per env-step x the launch's steps
+    tr = _traffic()
+    k = ((tr or {}).get('kernels') or {}).get(kname)
+    traffic = (k['hbm_bytes_per_launch'] / k.get('steps_per_launch', 1) * spl
+               if k and k.get('batch') == B else None)
+    rp = _rocprof_avg(kname, spl)
+    sq = (rp or {}).get('sq') or {}
+    # the fused env step is VALU/latency-bound (AI ~61 flop/B):
+    # headline = counted flops / kernel time vs the FP32 VALU peak; the HBM
+    # view (algorithmic bytes / kernel time vs 8 TB/s) is kept beside it
+    roofline = {'bound': 'valu', 'achieved': tflops, 'peak': FP32_VALU_PEAK_TFLOPS,
+                'unit': 'TFLOP/s', 'frac': tflops / FP32_VALU_PEAK_TFLOPS,
+                'traffic': traffic,
+                'kernel': kname, 'kernel_ms': kern_ms, 'steps_per_launch': spl,
+                'kernel_ms_per_step': kern_ms / spl,
+                'kernel_ms_source': kern_src,
+                'single_step_kernel_ms': single_ms,
+                # the SQ issue view of the same kernel (committed counters of
+                # this library build): VALU instructions x 4 cycles / wave cycles
+                'valu_issue_frac': sq.get('valu_issue_frac'),
+                'rocprof': rp,
+                'flops_per_launch': flops_per_launch,
+                'bytes_per_launch': bytes_per_launch,
+                'hbm': {'achieved': achieved_gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                        'frac': achieved_gbs / HBM_PEAK_GBS, 'traffic': traffic}}
   out = {
       'metric': 'env-steps/sec (Ant, 4096 envs/GPU)',
       'value': value,
@@ -857,30 +979,14 @@ def main():
       # RCCL all-gathers of the episodic (reward, done) sums inside the timed
       # region (0 at N = 1: there is no collective on one GPU)
       'collectives_in_timed_region': collectives,
-      # the fused env step is VALU/latency-bound (AI ~61 flop/B):
-      # headline = counted flops / kernel time vs the FP32 VALU peak; the HBM
-      # view (algorithmic bytes / kernel time vs 8 TB/s) is kept beside it
-      'roofline': {'bound': 'valu', 'achieved': tflops, 'peak': FP32_VALU_PEAK_TFLOPS,
-                   'unit': 'TFLOP/s', 'frac': tflops / FP32_VALU_PEAK_TFLOPS,
-                   'traffic': traffic,
-                   'kernel': kname, 'kernel_ms': kern_ms, 'steps_per_launch': spl,
-                   'kernel_ms_per_step': kern_ms / spl,
-                   'kernel_ms_source': kern_src,
-                   'single_step_kernel_ms': single_ms,
-                   # the SQ issue view of the same kernel (committed counters of
-                   # this library build): VALU instructions x 4 cycles / wave cycles
-                   'valu_issue_frac': sq.get('valu_issue_frac'),
-                   'rocprof': rp,
-                   'flops_per_launch': flops_per_launch,
-                   'bytes_per_launch': bytes_per_launch,
-                   'hbm': {'achieved': achieved_gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                           'frac': achieved_gbs / HBM_PEAK_GBS, 'traffic': traffic}},
   }
   # the same steps from the plain Python loop (one Env.step call per step):
   # host-bound on a slow host, hence the graph above
   # every loop's rate (value is the fastest); a loop that failed says why
   for kind, key in (('eager', 'eager_loop'), ('step', 'graph_loop'), ('rollout', 'rollout_loop'),
                     ('direct', 'direct_loop')):
+    if kind not in loops:
+      continue
     el, col, err = loops[kind]
     out[key] = ({'value': total / el, 'unit': 'env-steps/s', 'ms_per_step': el * 1e3 / args.steps,
                  'collectives_in_timed_region': col} if el is not None else {'error': err})
@@ -892,13 +998,18 @@ def main():
                               'only when it could not run')
   out['warmup_policy'] = (f'{args.warmup} warm-up steps; each replayed loop warms on >= '
                           f'{WARM_S * 1e3:.0f} ms of its own untimed replays (steady-state clocks)')
-  out['secondary_configs'] = None if args.no_secondary else secondary_configs(dev)
-  out['phase_roofline'] = (None if args.no_phases else
-                           phase_bench(env.unwrapped.sys, dev, args.phase_envs))
-  if world == 1 and not args.no_cpu_baseline:
-    out['cpu_baseline'] = cpu_baseline(B)
-  else:
-    out['cpu_baseline'] = None
+  out['full'] = bool(args.full)
+  if args.dump_outputs:
+    out['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped, 'loop': best}
+  if args.full:
+    out['roofline'] = roofline
+    out['secondary_configs'] = None if args.no_secondary else secondary_configs(dev)
+    out['phase_roofline'] = (None if args.no_phases else
+                             phase_bench(env.unwrapped.sys, dev, args.phase_envs))
+    if world == 1 and not args.no_cpu_baseline:
+      out['cpu_baseline'] = cpu_baseline(B)
+    else:
+      out['cpu_baseline'] = None
   print(json.dumps(out), flush=True)
   if dist is not None:
     dist.destroy_process_group()

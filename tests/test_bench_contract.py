@@ -38,6 +38,34 @@ def test_traffic_carries_algorithmic_bytes_per_env_kernel():
   assert hum['algorithmic_bytes_per_launch'] == 2284 * 4096
 
 
+def test_dump_outputs_writes_float_arrays_and_caps_the_size(tmp_path, monkeypatch):
+  """`--dump-outputs`: one float32 .npy per array; above the byte cap a
+  seeded sample of the envs, the same rows of every array on every run."""
+  import numpy as np
+  rng = np.random.default_rng(3)
+  arrays = {'obs': rng.standard_normal((50, 7)).astype(np.float32),
+            'pos': rng.standard_normal((50, 2, 3)).astype(np.float32),
+            'reward': rng.standard_normal(50).astype(np.float32)}
+  names = bench.dump_outputs(str(tmp_path / 'a'), dict(arrays))
+  assert names == ['obs', 'pos', 'reward']
+  for k, a in arrays.items():
+    got = np.load(tmp_path / 'a' / (k + '.npy'))
+    assert got.dtype == np.float32 and np.array_equal(got, a)
+  # 14 floats + the id per env: a 640-byte cap keeps 10 of the 50 envs
+  monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 640)
+  for d in ('b', 'c'):
+    assert bench.dump_outputs(str(tmp_path / d), dict(arrays)) == ['env_ids', 'obs', 'pos', 'reward']
+  ids = np.load(tmp_path / 'b' / 'env_ids.npy')
+  assert ids.dtype == np.float64 and len(ids) == 10 and len(set(ids)) == 10
+  assert np.array_equal(ids, np.load(tmp_path / 'c' / 'env_ids.npy'))
+  total = 0
+  for k, a in arrays.items():
+    got = np.load(tmp_path / 'b' / (k + '.npy'))
+    assert np.array_equal(got, a[ids.astype(int)])
+    total += got.nbytes
+  assert total + ids.nbytes <= 640
+
+
 def test_rank_plan_follows_gpus_and_the_launcher():
   """`--gpus N` is the experiment the line names: alone it spawns N ranks, a
   launcher's world must match it, and N = 1 runs in place."""

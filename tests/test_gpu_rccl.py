@@ -85,7 +85,7 @@ def test_bench_rccl_world1_under_torchrun():
   cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1',
          '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
          os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5',
-         '--no-secondary', '--no-phases', '--no-cpu-baseline']
+         '--full', '--no-secondary', '--no-phases', '--no-cpu-baseline']
   r = subprocess.run(cmd, env=_env(BX_DIST_FORCE='1'), capture_output=True, text=True,
                      timeout=170, cwd=ROOT)
   assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

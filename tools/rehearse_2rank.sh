@@ -10,10 +10,10 @@ mkdir -p gpurun_out
 TAG=${1:-r}; STEPS=${2:-20}; WARM=${3:-5}
 if [ "$MODE" = torchrun ]; then
   BX_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps $STEPS --warmup $WARM \
+    --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps $STEPS --warmup $WARM --full \
     --no-phases --no-secondary > gpurun_out/bench_2rank_$TAG.log 2>&1 || { tail -20 gpurun_out/bench_2rank_$TAG.log; exit 1; }
 else
-  BX_DIST_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps $STEPS --warmup $WARM \
+  BX_DIST_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps $STEPS --warmup $WARM --full \
     --no-phases --no-secondary > gpurun_out/bench_2rank_$TAG.log 2>&1 || { tail -20 gpurun_out/bench_2rank_$TAG.log; exit 1; }
 fi
 grep '^{' gpurun_out/bench_2rank_$TAG.log | python -c "

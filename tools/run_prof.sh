@@ -5,8 +5,8 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${1:-r01}
 OUT=gpurun_out/prof_$TAG
-ARGS="--steps 300 --warmup 30 --no-cpu-baseline --phase-envs 1048576"
-PARGS="--steps 50 --warmup 5 --no-cpu-baseline --phase-envs 1048576"
+ARGS="--steps 300 --warmup 30 --full --no-cpu-baseline --phase-envs 1048576"
+PARGS="--steps 50 --warmup 5 --full --no-cpu-baseline --phase-envs 1048576"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py $ARGS > $OUT.trace.log 2>&1 || { echo trace failed; tail -20 $OUT.trace.log; exit 1; }
 tail -1 $OUT.trace.log
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -o run --output-format csv -- python3 bench.py $PARGS > $OUT.fetch.log 2>&1 || { echo fetch failed; tail -20 $OUT.fetch.log; exit 1; }
