@@ -1,4 +1,3 @@
-#include <cstdio>
 // bx_capi.cpp — the C ABI (include/brax_amd.h): descriptor -> device blob,
 // argument validation, and stream-ordered kernel launches.
 #include <hip/hip_runtime.h>
@@ -6,6 +5,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <string>
@@ -91,7 +91,7 @@ struct Builder {
   void i(int o, int x) { w[o] = (uint32_t)x; }
 };
 
-// the system's feature mask (F_* of pbd_kernels.hip: what its joints,
+// the system's feature mask (F_* of pbd_features.h: what its joints,
 // actuators, colliders and layout need), which picks its step kernels
 static int system_feat(const bx_desc* d, const BlobHdr& H, int L, int J, int K, int G,
                        int max_groups, bool xcol, bool jh_off, bool r2, bool c16, bool r2g) {

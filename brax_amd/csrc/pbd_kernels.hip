@@ -1,4 +1,7 @@
-// pbd_kernels.hip — MI355X (gfx950) kernels of the PBD env stepper.
+// pbd_kernels.hip — MI355X (gfx950) kernels of the PBD env stepper: the
+// kernel bodies both translation units are built from. pbd_single.hip and
+// pbd_generic.hip define their identity (BX_TU_FAST / BX_TU_GENERIC), include
+// this file and add their own __global__ kernels and launchers.
 //
 // One fused launch runs a whole `Env.step` for a batch of environments:
 // `System._pbd_step` (brax/physics/system.py:254-325: actuators, joint damping,
@@ -14,6 +17,7 @@
 // item results are combined per body by deterministic gather lists (the
 // reference's `segment_sum`s), so the only HBM traffic is the QP in/out,
 // the action and the env-layer outputs.
+#pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -21,18 +25,11 @@
 
 #include <type_traits>
 
+#include "pbd_features.h"
 #include "pbd_launch.h"
 #include "pbd_layout.h"
 #include "pbd_math.h"
-
-// in-kernel stamps exist in the fast (SINGLE-mode) translation unit only
-#if !defined(BX_TU_FAST)
-#undef BX_STAMPS
-#endif
-// ... and the MULTI-mode ones in the item-loop translation unit only
-#if !defined(BX_TU_GENERIC)
-#undef BX_MSTAMPS
-#endif
+#include "pbd_stamps.h"
 
 namespace bx {
 
@@ -235,56 +232,6 @@ __device__ __forceinline__ JointC load_joint(const Cst& c, const BlobHdr& H, int
   return r;
 }
 
-// ---------------------------------------------------------------------------
-// compile-time feature mask: kernels specialised for a system only carry the
-// joint / actuator / contact kinds it uses (Ant: revolute + torque + one-way
-// capsule-plane), which keeps dead paths out of the register allocation.
-// ---------------------------------------------------------------------------
-enum { F_SPH = 1, F_ANGLE = 2, F_CC = 4, F_TW = 8, F_FORCE = 16, F_ALL = 31 };
-// F_G1 (outside F_ALL): every body's contact rows come from one collider
-// group, so the per-group normalisation needs one accumulator
-enum { F_G1 = 32 };
-// F_X (outside F_ALL): the extended contact functions (height map, clipped
-// plane, capsule-mesh, box-box SAT), item-loop kernels only. F_GEN: every
-// feature, the item-loop kernels' general instantiation.
-enum { F_X = 64, F_GEN = F_ALL | F_X };
-// F_R2 (outside F_ALL, SINGLE mode at 16 lanes): 17-32 contact rows, lane l
-// owning rows l and l + 16 (its second row's constants from the lane image's
-// LI_ROW2 words)
-enum { F_R2 = 256 };
-// F_C16 (outside F_ALL, SINGLE mode): contact gather lists of up to 16
-// entries (Pusher's wrist: 15 rows), the joint / actuator lists <= M
-enum { F_C16 = 512 };
-// F_R2G (with F_R2): the host put every one-way capsule-plane row in the
-// lanes' first slot and every two-way capsule-capsule row in the second, so
-// each slot's passes are compiled for its one contact function
-enum { F_R2G = 1024 };
-template <int F, int M> __device__ __forceinline__ constexpr int cl_width() {
-  return (F & F_C16) ? 16 : M;
-}
-template <int F> __device__ __forceinline__ bool is_rev(int type) {
-  if constexpr ((F & F_SPH) == 0) return true; else return type == 1;
-}
-template <int F> __device__ __forceinline__ bool is_torque(int type) {
-  if constexpr ((F & F_ANGLE) == 0) return true; else return type == 0;
-}
-// F_CCO (kernel-internal): every row this code path sees is a two-way
-// capsule-capsule row (F_R2G's second slot)
-enum { F_CCO = 2048 };
-template <int F> __device__ __forceinline__ bool is_plane(int fn) {
-  if constexpr ((F & F_CCO) != 0) return false;
-  else if constexpr ((F & F_CC) == 0) return true; else return fn == 0;
-}
-// the F_R2G kernels' two-way slot runs as contact halves (HALF: a row's a
-// side on lane k, its b side on lane k + 8; the host places them so)
-template <int F> __device__ __forceinline__ constexpr bool HALF() {
-  return (F & F_CCO) != 0 && (F & F_R2G) != 0;
-}
-template <int F> __device__ __forceinline__ bool is_oneway(int ow) {
-  if constexpr ((F & F_CCO) != 0) return false;
-  else if constexpr ((F & F_TW) == 0) return true; else return ow != 0;
-}
-
 // Joint.apply_angle_update (joints.py:130-152): the impulse p of an angular
 // correction dq; each side's rotation update is linear in it
 __device__ __forceinline__ v3 angle_impulse(const JointC& J, v3 dq) {
@@ -331,7 +278,6 @@ __device__ __forceinline__ v3 hinge_turn(v3 axis, v3 ref_p, v3 ref_c, const JLim
 // + 1 and LI_JLIM12 / 4 .. + 3) into LDS as 6 slots of L lanes (stage_lim):
 // li = the lane's slot-0 group, g = the row's first slot (LIM_G*). The empty
 // asm keeps every use a fresh LDS read rather than a hoisted register copy.
-enum { LIM_G0 = 0, LIM_G1 = 2, LIM_G2 = 4, LIM_SLOTS = 6 };
 template <int L>
 __device__ __forceinline__ JLim ld_lim(const uint4* li, int g) {
   asm volatile("" : "+s"(g));
@@ -1399,7 +1345,6 @@ __device__ __forceinline__ void act_torque(const JointC& Jc, const ActC& A, cons
 // instruction count of the joint and actuator phases (Ant leaves lanes 8-15
 // idle there otherwise).
 // ---------------------------------------------------------------------------
-enum { F_JH = 128 };
 
 // the partner half's value: lane ^ 8 within the env's 16-lane row
 // (bound_ctrl set: a row rotation has no invalid source lane, so the `old`
@@ -1833,23 +1778,6 @@ __device__ __forceinline__ RowC row_from_lds(const Env& E, int r) {
   return x;
 }
 
-#ifdef BX_MSTAMPS
-// (diagnostic: the MULTI stamps build splits the picks' phases into slots
-// 12-14 of the caller's accumulators)
-#define BX_NSTAMP(k)                                                               \
-  do {                                                                             \
-    if (nsa) {                                                                     \
-      __builtin_amdgcn_sched_barrier(0);                                           \
-      unsigned long long _t;                                                       \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");   \
-      __builtin_amdgcn_sched_barrier(0);                                           \
-      nsa[k] += _t - *nsl;                                                         \
-      *nsl = _t;                                                                   \
-    }                                                                              \
-  } while (0)
-#else
-#define BX_NSTAMP(k) do {} while (0)
-#endif
 // MT (the MULTI kernel): each row's group flags, Info index and centre pair
 // from the LDS-staged bounds (E.bimg), the keys' distances from the centres
 // placed this step (place_centres, before the call): no dependent L2 reads
@@ -2808,62 +2736,6 @@ __device__ __forceinline__ void vproj(QP& q, v3 ppos, q4 prot, const BodyC& B, f
   q.rot = nr;
 }
 
-#ifdef BX_STAMPS
-// per-workgroup accumulators (no atomics: contended atomics inside the timed
-// windows distort them); summed on the host by debug_stamps
-__device__ unsigned long long bx_stamp_wave[4096][16];
-#define BX_STAMP(k)                                                                \
-  do {                                                                             \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-    unsigned long long _t;                                                         \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");     \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-    st_acc[k] += _t - st_last;                                                     \
-    st_last = _t;                                                                  \
-  } while (0)
-// kernel-level stamps (env_step_kernel): slots 10..14; with BX_PSTAMPS the
-// prologue's parts too (slots 5..9, BX_KSTAMP(5..9); the pbd phases' slots
-// 0..9 are then not written)
-#define BX_KSTAMP_DECL                                                             \
-  unsigned long long kst_last, kst_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};       \
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(kst_last)::"memory");
-#define BX_KSTAMP(k)                                                               \
-  do {                                                                             \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-    unsigned long long _t;                                                         \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");     \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-    kst_acc[(k) - 5] += _t - kst_last;                                             \
-    kst_last = _t;                                                                 \
-    if ((k) == 14 && threadIdx.x == 0)                                             \
-      for (int _i = BX_KSLOT0; _i < 10; _i++) bx_stamp_wave[blockIdx.x & 4095][5 + _i] += kst_acc[_i]; \
-  } while (0)
-#if defined(BX_PSTAMPS)
-#define BX_KSLOT0 0
-#define BX_PSTAMP(k) BX_KSTAMP(k)
-#else
-#define BX_KSLOT0 5
-#define BX_PSTAMP(k) do {} while (0)
-#endif
-#elif defined(BX_PHASE_MARKS)
-// static per-phase instruction mix (diagnostic, tools/phase_mix.py): the
-// stamp points as assembly comments the scheduler does not move code across
-#define BX_STAMP(k)                                                                \
-  do {                                                                             \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-    asm volatile(";BXPHASE " #k ::: "memory");                                     \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-  } while (0)
-#define BX_KSTAMP_DECL
-#define BX_KSTAMP(k) BX_STAMP(k)
-#define BX_PSTAMP(k) do {} while (0)
-#else
-#define BX_STAMP(k) do {} while (0)
-#define BX_KSTAMP_DECL
-#define BX_KSTAMP(k) do {} while (0)
-#define BX_PSTAMP(k) do {} while (0)
-#endif
-
 // FOLD (the Ant / Humanoid / HalfCheetah env kernels; the host checks that every joint j
 // has torque actuator j): each joint's damping torque is added into its
 // actuator's slot, so the body phase gathers one list instead of two. The
@@ -3495,22 +3367,6 @@ struct RowInfoOut {
   int32_t* cell;  // the row's NearNeighbors cell (R_FLAT)
 };
 
-#ifdef BX_MSTAMPS
-// MULTI-mode phase stamps of each workgroup's first wave (diagnostic build)
-__device__ unsigned long long bx_mstamp_wave[4096][16];
-#define BX_MSTAMP(k)                                                               \
-  do {                                                                             \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-    unsigned long long _t;                                                         \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");     \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-    ms_acc[k] += _t - ms_last;                                                     \
-    ms_last = _t;                                                                  \
-  } while (0)
-#else
-#define BX_MSTAMP(k) do {} while (0)
-#endif
-
 template <int L, int F>
 __device__ void pbd_step_multi(const Cst& c, const BlobHdr& H, const Env& E, int lane, bool valid,
                                const float* act, int aw, const HoistM& X, RowInfoOut io,
@@ -4071,11 +3927,6 @@ __device__ void humanoid_com(const Cst& c, const BlobHdr& H, const float* qp, v3
 }
 
 // observation element i of the env kind
-// env-program specialisation: the hot env kinds get step kernels holding
-// only their own env code (EK_ANT, EK_HUM: Humanoid and HumanoidStandup,
-// EK_CHEETAH: HalfCheetah); EK_ANY carries every kind, chosen at run time
-// (EK_PUSHER: Pusher, round 6: its 50 substeps with the damping folded)
-enum { EK_ANY = 0, EK_ANT = 1, EK_HUM = 2, EK_CHEETAH = 3, EK_PUSHER = 4 };
 template <int EK>
 __device__ __forceinline__ constexpr bool ek_has(int k) {
   return EK == EK_ANY || (EK == EK_ANT && k == BX_ENV_ANT) ||
@@ -4366,22 +4217,7 @@ __device__ void env_observe(const Cst& c, const BlobHdr& H, const Env& E, int la
                             int flags, int obs_size, const float* act, int aw, float* obs_out,
                             const float* coef, const JointC* hj = nullptr,
                             const BodyC* hbody = nullptr, const ActC* hact = nullptr) {
-#if defined(BX_OSTAMPS) && defined(BX_TU_FAST)
-  // (diagnostic: the observation's parts into stamp slots 5..9)
-  unsigned long long ost_last;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ost_last)::"memory");
-#define BX_OST(k)                                                                  \
-  do {                                                                             \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-    unsigned long long _t;                                                         \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");     \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-    if (threadIdx.x == 0) bx_stamp_wave[blockIdx.x & 4095][k] += _t - ost_last;    \
-    ost_last = _t;                                                                 \
-  } while (0)
-#else
-#define BX_OST(k) do {} while (0)
-#endif
+  BX_OST_DECL
   joint_angles<L>(c, H, E, lane, hj);
   BX_OST(0);
   if ((KIND_IS(BX_ENV_HUMANOID) || KIND_IS(BX_ENV_HUMANOID_STANDUP)) && lane == 0) {
@@ -4517,11 +4353,6 @@ __device__ void env_observe(const Cst& c, const BlobHdr& H, const Env& E, int la
 
 
 
-// kernel variants: MODE_GLOBAL (constants read from the HBM blob inside the
-// loops), MODE_SINGLE (constants hoisted to registers), MODE_LDS (the blob's
-// constant part copied to LDS once per workgroup, read there inside the loops)
-enum { MODE_GLOBAL = 0, MODE_SINGLE = 1, MODE_LDS = 2, MODE_MULTI = 3 };
-
 // step kernels: optional register-budget hint (A/B knob, BX_WAVES1)
 #if defined(BX_WAVES1)
 #define BX_STEP_ATTR __attribute__((amdgpu_waves_per_eu(1, 1)))
@@ -4656,17 +4487,6 @@ __device__ __forceinline__ void system_step_body(const StepArgs& A) {
 template <int L, int MODE, int F, int M>
 __global__ void __launch_bounds__(L > 64 ? L : 64) BX_STEP_ATTR system_step_kernel(StepArgs A) {
   system_step_body<L, MODE, F, M>(A);
-}
-// the MULTI kernel held to 256 registers per lane (VGPRs + AGPRs): two waves
-// per SIMD. Past 256 (round 4: the row image's b-slot index took it to
-// 256 + 4) one wave per SIMD fits and the CU holds half the envs: Ant
-// Mountain(4) at 2,048 envs ran 1.8x slower (tools/multi_occ.py). At L = 128
-// threads per env (two waves) four envs share a CU, when their LDS tail
-// fits 40 KB (the compact contact slots, bx_capi.cpp)
-template <int L, int JH = 0>
-__global__ void __launch_bounds__(L) __attribute__((amdgpu_waves_per_eu(2)))
-system_step_multi_kernel(StepArgs A) {
-  system_step_body<L, MODE_MULTI, F_CC | F_TW | JH, 1>(A);
 }
 
 
@@ -5256,601 +5076,5 @@ template <int L, int MODE, int F, int M, int EK = EK_ANY>
 __global__ void __launch_bounds__(L > 64 ? L : 64) BX_STEP_ATTR env_step_kernel(EnvArgs A) {
   env_step_body<L, MODE, F, M, EK>(A);
 }
-// one step on the packed layout (bx_env_step_packed: Env.step's host path)
-// through the PK body, under its own name (the benchmarked envs' kernels)
-template <int L, int MODE, int F, int M, int EK = EK_ANY>
-__global__ void __launch_bounds__(L > 64 ? L : 64) BX_STEP_ATTR env_step_packed_kernel(EnvArgs A) {
-  env_step_body<L, MODE, F, M, EK, true, true>(A);
-}
-// the Ant step kernel held to 256 registers (2 waves per SIMD) for batches
-// past one wave per SIMD: at 4,096 envs the unbounded kernel's single wave
-// per SIMD is 7 % faster (29.8 vs 32.0 us), but at 32,768 envs (8 waves per
-// SIMD) it runs 8 residency rounds against this one's 4 (152 vs 219 M
-// env-steps/s, tools/ab_ant_waves.sh)
-template <int L, int MODE, int F, int M, int EK = EK_ANY>
-__global__ void __launch_bounds__(L > 64 ? L : 64) __attribute__((amdgpu_waves_per_eu(2)))
-env_step_wide_kernel(EnvArgs A) {
-  env_step_body<L, MODE, F, M, EK>(A);
-}
-template <int L, int MODE, int F, int M, int EK = EK_ANY>
-__global__ void __launch_bounds__(L > 64 ? L : 64) __attribute__((amdgpu_waves_per_eu(2)))
-env_rollout_wide_kernel(EnvArgs A) {
-  env_step_body<L, MODE, F, M, EK, true>(A);
-}
-// the same body under its own name for multi-step launches of the
-// benchmarked envs' kernels (bx_env_rollout_packed), so a profile tells
-// K-step launches from single steps
-template <int L, int MODE, int F, int M, int EK = EK_ANY>
-__global__ void __launch_bounds__(L > 64 ? L : 64) BX_STEP_ATTR env_rollout_kernel(EnvArgs A) {
-  env_step_body<L, MODE, F, M, EK, true>(A);
-}
-
-// System.info contact part + optional Env._get_obs of the same state (reset)
-template <int L>
-__global__ void __launch_bounds__(L > 64 ? L : 64) info_obs_kernel(InfoArgs A) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  Cst c{A.blob};
-  BlobHdr H = *reinterpret_cast<const BlobHdr*>(A.blob);
-  const int lane = threadIdx.x % L;
-  const int le = threadIdx.x / L;
-  const int64_t e = (int64_t)blockIdx.x * (blockDim.x / L) + le;
-  const bool valid = e < A.n_envs;
-  Env E = carve(smem + le * H.env_words, H);
-  if (valid) {
-    for (int b = lane; b < H.N; b += L) load_qp_global(A.q, e, b, E.qp + b * QP_STRIDE);
-  } else {
-    for (int b = lane; b < H.N; b += L) {
-      float* s = E.qp + b * QP_STRIDE;
-      for (int k = 0; k < 13; k++) s[k] = k == 3 ? 1.f : 0.f;
-    }
-  }
-  esync<L>();
-  if (A.angle) {  // Joint.angle_vel only
-    joint_angles<L>(c, H, E, lane);
-    esync<L>();
-    if (valid)
-      for (int i = lane; i < H.D; i += L) {
-        A.angle[e * H.D + i] = E.ang[i];
-        A.angvel[e * H.D + i] = E.ang[H.D + i];
-      }
-    return;
-  }
-  pbd_info<L>(c, H, E, lane);
-  if (valid) {
-    for (int b = lane; b < H.N; b += L) {
-      const float* acc = E.acc + b * ACC_STRIDE;
-      const bx_info& I = A.info;
-      if (I.contact_vel.ptr) {
-        float* p = I.contact_vel.ptr + e * I.contact_vel.env_stride + b * I.contact_vel.body_stride;
-        p[0] = acc[ACC_ICV]; p[1] = acc[ACC_ICV + 1]; p[2] = acc[ACC_ICV + 2];
-      }
-      if (I.contact_ang.ptr) {
-        float* p = I.contact_ang.ptr + e * I.contact_ang.env_stride + b * I.contact_ang.body_stride;
-        p[0] = acc[ACC_ICA]; p[1] = acc[ACC_ICA + 1]; p[2] = acc[ACC_ICA + 2];
-      }
-    }
-  }
-  if (A.obs) {
-    const float* act = valid && A.act ? A.act + e * A.act_stride : nullptr;
-    env_observe<L>(c, H, E, lane, A.kind, A.obs_flags, A.obs_size, act, (int)A.act_width,
-                   valid ? A.obs + e * A.obs_size : nullptr, A.coef);
-  }
-  // reset: reward, done, steps, truncation and metrics start at zero
-  // (ant.py:205-219, wrappers.py:94-97)
-  if (valid) {
-    if (lane == 0) {
-      if (A.zero_reward) A.zero_reward[e] = 0.f;
-      if (A.zero_done) A.zero_done[e] = 0.f;
-      if (A.zero_steps) A.zero_steps[e] = 0.f;
-      if (A.zero_trunc) A.zero_trunc[e] = 0.f;
-    }
-    if (A.zero_metrics)
-      for (int i = lane; i < A.n_metrics; i += L) A.zero_metrics[e * A.n_metrics + i] = 0.f;
-  }
-}
-
-
-// System.default_qp (system.py:112-242): one thread per env (reset path)
-
-
-#if !defined(BX_TU_FAST)  // reset / RNG kernels: the generic translation unit
-__global__ void __launch_bounds__(64) default_qp_kernel(ResetArgs A) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  Cst c{A.blob};
-  BlobHdr H = *reinterpret_cast<const BlobHdr*>(A.blob);
-  const int64_t e = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (e >= A.n_envs) return;
-  float* q = smem + threadIdx.x * H.N * 13;  // per-thread scratch: N x 13
-  const int N = H.N, D = H.num_joint_dof;
-  for (int b = 0; b < N; b++)
-    for (int k = 0; k < 13; k++) q[b * 13 + k] = c.f(H.o_base + b * 13 + k);
-  const float* ja = A.gen ? nullptr : A.angle + e * D;
-  const float* jv = A.gen ? nullptr : A.vel + e * D;
-  // Env.reset draws (gen = 1), keyed by the global env id g (W draws per
-  // env: (seed, g * W + k)) or by the env's own key (seeds[e], k):
-  //   default (ant.py:200-203 ...): qpos = default + U[-s, s) at k = dof,
-  //     qvel = U[-s, s) at k = D + dof (W = 2D)
-  //   REACHER, REACHERANGLE (reacher.py:157-160): qpos noise U[-.1, .1),
-  //     qvel U[-.005, .005), then the target's two draws at 2D, 2D + 1
-  //   PUSHER (pusher.py:178-195): default angles, qvel U[-.005, .005) on the
-  //     first D - 4 dofs (k = dof), the object's two draws at D - 4, D - 3
-  //   UR5E, FETCH (ur5e.py:41-46): default pose at rest, the target's two
-  //     draws at 0, 1;  GRASP (grasp.py:54-70): default pose at rest
-  const int kind = A.gen ? A.kind : 0;
-  int W = 2 * D;
-  float as = A.scale, vs = A.scale;
-  int nvel = D;
-  if (kind == BX_ENV_REACHER || kind == BX_ENV_REACHERANGLE) {
-    W = 2 * D + 2; as = .1f; vs = .005f;
-  } else if (kind == BX_ENV_PUSHER) {
-    W = D - 4 + 2; as = 0.f; vs = .005f; nvel = D - 4;
-  } else if (kind == BX_ENV_UR5E || kind == BX_ENV_FETCH) {
-    W = 2; as = 0.f; vs = 0.f; nvel = 0;
-  } else if (kind == BX_ENV_GRASP) {
-    W = 0; as = 0.f; vs = 0.f; nvel = 0;
-  }
-  const int voff = kind == BX_ENV_PUSHER ? 0 : D;  // pusher's qvel draws come first
-  const uint64_t seed = A.seeds ? A.seeds[e] : A.seed;
-  const uint64_t g0 = A.seeds ? 0ull : (uint64_t)(A.env_offset + e) * (uint64_t)W;
-  for (int f = 0; f < H.n_fk; f++) {
-    int o = H.o_fk + f * FK_STRIDE;
-    float a3[3], v3_[3];
-    for (int l = 0; l < 3; l++) {
-      int ix = c.i(o + FK_IDX + l);
-      if (A.gen) {
-        a3[l] = ix < 0 ? 0.f
-                : c.f(H.o_dangle + ix) + (as > 0.f ? uniform_at(seed, g0 + ix, -as, as) : 0.f);
-        v3_[l] = ix >= 0 && ix < nvel ? uniform_at(seed, g0 + voff + ix, -vs, vs) : 0.f;
-      } else {
-        a3[l] = ix >= 0 ? ja[ix] : 0.f;
-        v3_[l] = ix >= 0 ? jv[ix] : 0.f;
-      }
-    }
-    q4 jr{c.f(o + FK_ROT), c.f(o + FK_ROT + 1), c.f(o + FK_ROT + 2), c.f(o + FK_ROT + 3)};
-    q4 rot{c.f(o + FK_REF), c.f(o + FK_REF + 1), c.f(o + FK_REF + 2), c.f(o + FK_REF + 3)};
-    v3 axes[3] = {rotate(mk(1.f, 0.f, 0.f), jr), rotate(mk(0.f, 1.f, 0.f), jr),
-                  rotate(mk(0.f, 0.f, 1.f), jr)};
-    v3 lang = axes[0] * v3_[0] + axes[1] * v3_[1] + axes[2] * v3_[2];
-    for (int l = 0; l < 3; l++) {
-      v3 ax = rotate(axes[l], rot);
-      rot = quat_mul(quat_rot_axis(ax, a3[l]), rot);
-    }
-    int bp = c.i(o + FK_BP), bc = c.i(o + FK_BC);
-    float* sp = q + bp * 13;
-    float* sc = q + bc * 13;
-    q4 prot = ld4(sp + 3);
-    q4 wr = quat_mul(prot, rot);
-    v3 lp = c.f3(o + FK_OFFP) - rotate(c.f3(o + FK_OFFC), rot);
-    v3 wp = ld3(sp) + rotate(lp, prot);
-    v3 wa = rotate(lang, prot);
-    st3(sc, wp);
-    st4(sc + 3, wr);
-    st3(sc + 10, wa);
-  }
-  // bodies.min_z per root group, then lift (system.py:213-240)
-  for (int g = 0; g < H.n_root_groups; g++) {
-    float zmin = 3.4028235e38f;
-    for (int b = 0; b < N; b++) {
-      if (c.i(H.o_rgroup + b) != g) continue;
-      float bz = 3.4028235e38f;
-      for (int p = c.i(H.o_zoff + b), pe = c.i(H.o_zoff + b + 1); p < pe; p++) {
-        int o = H.o_zpt + p * 4;
-        v3 w = rotate(c.f3(o), ld4(q + b * 13 + 3));
-        float z = q[b * 13 + 2] + w.z - c.f(o + 3);
-        bz = fminf(bz, z);
-      }
-      if (c.i(H.o_zero + b)) bz = fminf(bz, 0.f);
-      zmin = fminf(zmin, bz);
-    }
-    for (int b = 0; b < N; b++) {
-      if (c.i(H.o_rgroup + b) != g) continue;
-      q[b * 13 + 0] = q[b * 13 + 0] - zmin * 0.f;
-      q[b * 13 + 1] = q[b * 13 + 1] - zmin * 0.f;
-      q[b * 13 + 2] = q[b * 13 + 2] - zmin * 1.f;
-    }
-  }
-  // the bodies the env's reset places after default_qp (index_update of
-  // qp.pos, so after the lift): the reachers' target (reacher.py:212-221,
-  // reacherangle.py:102-113: radius .2 u, sqrt(u) for ReacherAngle), the
-  // pusher's object in its .17 disc, goal and table (pusher.py:181-201), the
-  // target envs' target on their ring (ur5e.py:117-125, fetch.py:124-134)
-  const float twopi = 3.14159265358979323846f * 2.f;
-  if (kind == BX_ENV_REACHER || kind == BX_ENV_REACHERANGLE) {
-    const float u0 = uniform_at(seed, g0 + 2 * D, 0.f, 1.f);
-    const float u1 = uniform_at(seed, g0 + 2 * D + 1, 0.f, 1.f);
-    const float dist = .2f * (kind == BX_ENV_REACHERANGLE ? sqrtf(u0) : u0);
-    const float an = twopi * u1;
-    float* t = q + (int)A.coef[0] * 13;
-    t[0] = dist * cosf(an);
-    t[1] = dist * sinf(an);
-    t[2] = .01f;
-  } else if (kind == BX_ENV_PUSHER) {
-    float x = uniform_at(seed, g0 + D - 4, -.3f, 0.f);
-    float y = uniform_at(seed, g0 + D - 3, -.2f, .2f);
-    const float nrm = sqrtf(x * x + y * y);
-    const float sc = nrm > .17f ? .17f / nrm : 1.f;
-    float* ob = q + (int)A.coef[1] * 13;
-    ob[0] = sc * x;
-    ob[1] = sc * y;
-    ob[2] = .05f;
-    float* gl = q + (int)A.coef[2] * 13;
-    gl[0] = .45f; gl[1] = .05f; gl[2] = .05f;
-    float* tb = q + (int)A.coef[3] * 13;
-    tb[0] = 0.f; tb[1] = 0.f; tb[2] = 0.f;
-  } else if (kind == BX_ENV_UR5E || kind == BX_ENV_FETCH) {
-    const float u0 = uniform_at(seed, g0, 0.f, 1.f), u1 = uniform_at(seed, g0 + 1, 0.f, 1.f);
-    const float rr = A.coef[2] + A.coef[3] * u0;
-    const float an = twopi * u1;
-    float* t = q + (int)A.coef[1] * 13;
-    t[0] = rr * cosf(an);
-    t[1] = rr * sinf(an);
-    t[2] = A.coef[4];
-  }
-  // the target envs' per-env stream (info['rng']): a hash of (seed, global
-  // env id), or of the env's own key
-  if (A.rng_out && (kind == BX_ENV_UR5E || kind == BX_ENV_FETCH || kind == BX_ENV_GRASP)) {
-    const uint64_t id = A.seeds ? 0ull : (uint64_t)(A.env_offset + e);
-    int64_t z = (int64_t)(id * 0x9E3779B97F4A7C15ull + (seed & 0x7FFFFFFFFFFFFFFFull));
-    z = (int64_t)((uint64_t)(z ^ (z >> 31)) * 0x94D049BB133111EBull);
-    A.rng_out[e] = (uint32_t)(z ^ (z >> 29));
-  }
-  for (int b = 0; b < N; b++) store_qp_global(A.out, e, b, q + b * 13);
-}
-
-// counter-based uniform fill: splitmix64 of (seed, index) -> [lo, hi)
-__global__ void uniform_kernel(float* out, int64_t n, uint64_t seed, uint64_t offset, float lo,
-                               float hi) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  out[i] = uniform_at(seed, (uint64_t)i + offset, lo, hi);
-}
-
-// the same fill over n_slabs slabs of slab_n elements with their own offsets,
-// advanced by a device-resident epoch counter: out[s * slab_n + j] =
-// U(seed, offset + epoch * epoch_stride + s * slab_stride + j). A
-// graph-captured rollout draws the action slabs of all its K steps in one
-// launch and still draws fresh slabs per replay (the counter is bumped inside
-// the graph); epoch null reads as 0
-__global__ void uniform_slabs_kernel(float* out, int64_t slab_n, int64_t n, uint64_t seed,
-                                     uint64_t offset, uint64_t slab_stride,
-                                     const int64_t* __restrict__ epoch, uint64_t epoch_stride,
-                                     float lo, float hi) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint64_t e = epoch ? (uint64_t)epoch[0] : 0ull;
-  const int64_t sl = i / slab_n, j = i - sl * slab_n;
-  out[i] = uniform_at(seed, offset + e * epoch_stride + (uint64_t)sl * slab_stride + (uint64_t)j,
-                      lo, hi);
-}
-
-#endif
-
-}  // namespace bx
-
-// ---------------------------------------------------------------------------
-// launch helpers (host)
-// ---------------------------------------------------------------------------
-namespace bx {
-
-// compute units of the current device (the launch runs under the system's
-// device scope), cached per device
-static int cu_count() {
-  static int cached[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (!cached[dev]) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cached[dev] = n;
-  }
-  return cached[dev];
-}
-
-template <typename Args>
-static void launch_one(void (*k)(Args), dim3 grid, int tpb, size_t lds, hipStream_t s, const Args& a) {
-  // tpb threads per workgroup (a multiple of L, <= 64): 64 / L envs share a
-  // wavefront by default; 32 halves that (twice the waves for one batch)
-  if (lds > 65536) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, grid, dim3(tpb), lds, s, a);
-}
-
-// instantiated variants: (lanes, mode, features, gather width). This file is
-// compiled twice (Makefile): BX_TU_FAST holds the register-hoisted SINGLE-mode
-// kernels; BX_TU_GENERIC holds the item-loop kernels (large scenes,
-// legacy_spring, the extended contact functions) and the reset / info
-// kernels. Both are built with fast reciprocal division by default
-// (GENERIC_PRECISE=1: IEEE division in the second). Single mode at 16 lanes is
-// specialised per feature set and gather width.
-#define BX_SINGLE16(KERNEL, ARGS, M)                                                \
-  switch (feat) {                                                                   \
-    case 0: launch_one<ARGS>(KERNEL<16, 1, 0, M>, grid, tpb, lds, s, a); break;     \
-    case F_SPH: launch_one<ARGS>(KERNEL<16, 1, F_SPH, M>, grid, tpb, lds, s, a); break; \
-    case F_G1: launch_one<ARGS>(KERNEL<16, 1, F_G1, M>, grid, tpb, lds, s, a); break; \
-    case F_SPH | F_G1: launch_one<ARGS>(KERNEL<16, 1, F_SPH | F_G1, M>, grid, tpb, lds, s, a); break; \
-    case F_CC | F_TW: launch_one<ARGS>(KERNEL<16, 1, F_CC | F_TW, M>, grid, tpb, lds, s, a); break; \
-    case F_CC | F_TW | F_G1: launch_one<ARGS>(KERNEL<16, 1, F_CC | F_TW, M>, grid, tpb, lds, s, a); break; \
-    case F_G1 | F_JH: launch_one<ARGS>(KERNEL<16, 1, F_G1 | F_JH, M>, grid, tpb, lds, s, a); break; \
-    case F_JH: launch_one<ARGS>(KERNEL<16, 1, F_JH, M>, grid, tpb, lds, s, a); break; \
-    case F_CC | F_TW | F_JH: \
-    case F_CC | F_TW | F_G1 | F_JH: launch_one<ARGS>(KERNEL<16, 1, F_CC | F_TW | F_JH, M>, grid, tpb, lds, s, a); break; \
-    default: launch_one<ARGS>(KERNEL<16, 1, F_ALL, M>, grid, tpb, lds, s, a); break; \
-  }
-// F_R2 systems (17-32 rows at 16 lanes): HalfCheetah (capsule-capsule,
-// two-way, joint halves), Fetch (box corners, one group), HumanoidStandup
-// (spherical, one group), else every feature
-#define BX_SINGLE16_R2(KERNEL, ARGS, M)                                             \
-  if (feat & F_C16) {                                                               \
-    if ((feat & ~(F_R2 | F_C16 | F_G1 | F_R2G)) == (F_CC | F_TW | F_JH) && (feat & F_R2G)) \
-      launch_one<ARGS>(KERNEL<16, 1, F_CC | F_TW | F_JH | F_R2 | F_C16 | F_R2G, M>, grid, tpb, lds, s, a); \
-    else if ((feat & ~(F_R2 | F_C16 | F_G1 | F_R2G)) == (F_CC | F_TW | F_JH))      \
-      launch_one<ARGS>(KERNEL<16, 1, F_CC | F_TW | F_JH | F_R2 | F_C16, M>, grid, tpb, lds, s, a); \
-    else                                                                            \
-      launch_one<ARGS>(KERNEL<16, 1, F_ALL | F_R2 | F_C16, M>, grid, tpb, lds, s, a); \
-  } else                                                                            \
-  switch (feat & ~F_R2) {                                                           \
-    case F_CC | F_TW | F_JH | F_R2G:                                                \
-    case F_CC | F_TW | F_G1 | F_JH | F_R2G: launch_one<ARGS>(KERNEL<16, 1, F_CC | F_TW | F_JH | F_R2 | F_R2G, M>, grid, tpb, lds, s, a); break; \
-    case F_CC | F_TW | F_JH:                                                        \
-    case F_CC | F_TW | F_G1 | F_JH: launch_one<ARGS>(KERNEL<16, 1, F_CC | F_TW | F_JH | F_R2, M>, grid, tpb, lds, s, a); break; \
-    case F_G1: launch_one<ARGS>(KERNEL<16, 1, F_G1 | F_R2, M>, grid, tpb, lds, s, a); break; \
-    case F_SPH | F_G1: launch_one<ARGS>(KERNEL<16, 1, F_SPH | F_G1 | F_R2, M>, grid, tpb, lds, s, a); break; \
-    default: launch_one<ARGS>(KERNEL<16, 1, F_ALL | F_R2, M>, grid, tpb, lds, s, a); break; \
-  }
-#define BX_DISPATCH_SINGLE(KERNEL, ARGS)                                            \
-  if (L == 16 && (feat & F_R2)) {                                                   \
-    if (gw <= 4) { BX_SINGLE16_R2(KERNEL, ARGS, 4) } else { BX_SINGLE16_R2(KERNEL, ARGS, 8) } \
-  } else if (L == 16 && (feat & F_C16)) {                                           \
-    if (gw <= 4) launch_one<ARGS>(KERNEL<16, 1, F_ALL | F_C16, 4>, grid, tpb, lds, s, a); \
-    else launch_one<ARGS>(KERNEL<16, 1, F_ALL | F_C16, 8>, grid, tpb, lds, s, a);     \
-  } else if (L == 16) {                                                             \
-    if (gw <= 4) { BX_SINGLE16(KERNEL, ARGS, 4) } else { BX_SINGLE16(KERNEL, ARGS, 8) } \
-  } else if (L == 32) {                                                             \
-    launch_one<ARGS>(KERNEL<32, 1, F_ALL, 8>, grid, tpb, lds, s, a);                \
-  } else {                                                                          \
-    launch_one<ARGS>(KERNEL<64, 1, F_ALL, 8>, grid, tpb, lds, s, a);                \
-  }
-// item-loop kernels: a lean instantiation (revolute joints, torque
-// actuators, capsule-plane / capsule-capsule rows one- or two-way, no forces:
-// Ant Mountain, the culled scenes) where the system allows, else every feature
-#define F_LEAN (F_CC | F_TW)
-#define BX_DISPATCH_GENERIC(KERNEL, ARGS)                                           \
-  const bool lean = (feat & (F_SPH | F_ANGLE | F_FORCE | F_X)) == 0;                \
-  switch (L * 8 + mode * 2 + (lean ? 1 : 0)) {                                      \
-    case 16 * 8 + 0: case 16 * 8 + 1: launch_one<ARGS>(KERNEL<16, 0, F_GEN, 8>, grid, tpb, lds, s, a); break; \
-    case 16 * 8 + 4: case 16 * 8 + 5: launch_one<ARGS>(KERNEL<16, 2, F_GEN, 8>, grid, tpb, lds, s, a); break; \
-    case 32 * 8 + 0: case 32 * 8 + 1: launch_one<ARGS>(KERNEL<32, 0, F_GEN, 8>, grid, tpb, lds, s, a); break; \
-    case 32 * 8 + 4: case 32 * 8 + 5: launch_one<ARGS>(KERNEL<32, 2, F_GEN, 8>, grid, tpb, lds, s, a); break; \
-    case 64 * 8 + 0: launch_one<ARGS>(KERNEL<64, 0, F_GEN, 8>, grid, tpb, lds, s, a); break; \
-    case 64 * 8 + 1: launch_one<ARGS>(KERNEL<64, 0, F_LEAN, 8>, grid, tpb, lds, s, a); break; \
-    case 64 * 8 + 4: case 64 * 8 + 5: launch_one<ARGS>(KERNEL<64, 2, F_GEN, 8>, grid, tpb, lds, s, a); break; \
-    case 128 * 8 + 0: launch_one<ARGS>(KERNEL<128, 0, F_GEN, 8>, grid, tpb, lds, s, a); break; \
-    case 128 * 8 + 1: launch_one<ARGS>(KERNEL<128, 0, F_LEAN, 8>, grid, tpb, lds, s, a); break; \
-    case 256 * 8 + 0: launch_one<ARGS>(KERNEL<256, 0, F_GEN, 8>, grid, tpb, lds, s, a); break; \
-    case 256 * 8 + 1: launch_one<ARGS>(KERNEL<256, 0, F_LEAN, 8>, grid, tpb, lds, s, a); break; \
-    default: return hipErrorInvalidValue;                                           \
-  }
-
-#if defined(BX_TU_FAST)
-hipError_t launch_system_step_single(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
-                                     hipStream_t s, const StepArgs& a) {
-  const int epb = tpb / L;
-  dim3 grid((unsigned)((n_envs + epb - 1) / epb));
-  BX_DISPATCH_SINGLE(system_step_kernel, StepArgs)
-  return hipGetLastError();
-}
-// single_kernel_feat: BX_DISPATCH_SINGLE run over a host-side probe that
-// records the instantiation's F instead of launching it (the same decision)
-struct ProbeArgs {
-  int* out;
-};
-template <int PL, int PMODE, int PF, int PM>
-void probe_kernel(ProbeArgs a) { *a.out = PF; }
-template <>
-void launch_one<ProbeArgs>(void (*k)(ProbeArgs), dim3, int, size_t, hipStream_t, const ProbeArgs& a) {
-  k(a);
-}
-int single_kernel_feat(int L, int feat, int gw) {
-  int f = -1;
-  const ProbeArgs a{&f};
-  const dim3 grid(1);
-  const int tpb = 64;
-  const size_t lds = 0;
-  hipStream_t s = nullptr;
-  BX_DISPATCH_SINGLE(probe_kernel, ProbeArgs)
-  return f;
-}
-hipError_t launch_env_step_single(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
-                                  hipStream_t s, const EnvArgs& a, int fold) {
-  const int epb = tpb / L;
-  dim3 grid((unsigned)((n_envs + epb - 1) / epb));
-  // the benchmarked envs get kernels holding only their own env program
-  const int k = a.P.kind;
-  // (their kernels fold each joint's damping into its actuator's slot: fold
-  // bit 0 = every joint j has torque actuator j; the joint-halves kernels
-  // also give each side lane its body's copy: bit 1 = the system allows it)
-  const bool jb = (fold & 2) != 0;
-  if (fold && jb && L == 16 && gw <= 4 && k == BX_ENV_ANT && feat == (F_G1 | F_JH)) {
-    // past one wave per SIMD: the register-capped kernels
-    const bool wide = (int64_t)grid.x * (tpb / 64 > 0 ? tpb / 64 : 1) > 4 * (int64_t)cu_count();
-    // (a packed single step at a wide batch takes the wide rollout kernel)
-    if ((a.n_steps > 1 || a.packed) && wide)
-      launch_one<EnvArgs>(env_rollout_wide_kernel<16, 1, F_G1 | F_JH, 4, EK_ANT>, grid, tpb, lds, s, a);
-    else if (a.n_steps > 1)
-      launch_one<EnvArgs>(env_rollout_kernel<16, 1, F_G1 | F_JH, 4, EK_ANT>, grid, tpb, lds, s, a);
-    else if (wide)
-      launch_one<EnvArgs>(env_step_wide_kernel<16, 1, F_G1 | F_JH, 4, EK_ANT>, grid, tpb, lds, s, a);
-    else if (a.packed)
-      launch_one<EnvArgs>(env_step_packed_kernel<16, 1, F_G1 | F_JH, 4, EK_ANT>, grid, tpb, lds, s, a);
-    else
-      launch_one<EnvArgs>(env_step_kernel<16, 1, F_G1 | F_JH, 4, EK_ANT>, grid, tpb, lds, s, a);
-    return hipGetLastError();
-  }
-  if (fold && L == 16 && gw <= 4 && (k == BX_ENV_HUMANOID || k == BX_ENV_HUMANOID_STANDUP) &&
-      feat == (F_SPH | F_G1)) {
-    if (a.n_steps > 1)
-      launch_one<EnvArgs>(env_rollout_kernel<16, 1, F_SPH | F_G1, 4, EK_HUM>, grid, tpb, lds, s, a);
-    else if (a.packed)
-      launch_one<EnvArgs>(env_step_packed_kernel<16, 1, F_SPH | F_G1, 4, EK_HUM>, grid, tpb, lds, s, a);
-    else
-      launch_one<EnvArgs>(env_step_kernel<16, 1, F_SPH | F_G1, 4, EK_HUM>, grid, tpb, lds, s, a);
-    return hipGetLastError();
-  }
-  // HalfCheetah: 16 one-way ground rows in slot 1, the feet's capsule-capsule
-  // row in slot 2 (F_R2 | F_R2G), joint halves
-  constexpr int F_CHEETAH = F_CC | F_TW | F_JH | F_R2 | F_R2G;
-  if (fold && jb && L == 16 && gw <= 4 && k == BX_ENV_HALFCHEETAH && (feat & ~F_G1) == F_CHEETAH) {
-    if (a.n_steps > 1)
-      launch_one<EnvArgs>(env_rollout_kernel<16, 1, F_CHEETAH, 4, EK_CHEETAH>, grid, tpb, lds, s, a);
-    else if (a.packed)
-      launch_one<EnvArgs>(env_step_packed_kernel<16, 1, F_CHEETAH, 4, EK_CHEETAH>, grid, tpb, lds, s, a);
-    else
-      launch_one<EnvArgs>(env_step_kernel<16, 1, F_CHEETAH, 4, EK_CHEETAH>, grid, tpb, lds, s, a);
-    return hipGetLastError();
-  }
-  // Pusher: 16 one-way plane rows in slot 1, 7 two-way capsule-capsule rows
-  // as contact halves in slot 2, 16-entry contact lists, joint halves, the
-  // damping folded (no body copies: F_C16)
-  constexpr int F_PUSHER = F_CC | F_TW | F_JH | F_R2 | F_C16 | F_R2G;
-  if (fold && L == 16 && k == BX_ENV_PUSHER && (feat & ~F_G1) == F_PUSHER) {
-#define BX_PUSHER_LAUNCH(MW)                                                                        \
-    if (a.n_steps > 1)                                                                              \
-      launch_one<EnvArgs>(env_rollout_kernel<16, 1, F_PUSHER, MW, EK_PUSHER>, grid, tpb, lds, s, a); \
-    else if (a.packed)                                                                              \
-      launch_one<EnvArgs>(env_step_packed_kernel<16, 1, F_PUSHER, MW, EK_PUSHER>, grid, tpb, lds, s, a); \
-    else                                                                                            \
-      launch_one<EnvArgs>(env_step_kernel<16, 1, F_PUSHER, MW, EK_PUSHER>, grid, tpb, lds, s, a);
-    if (gw <= 4) { BX_PUSHER_LAUNCH(4) } else { BX_PUSHER_LAUNCH(8) }
-#undef BX_PUSHER_LAUNCH
-    return hipGetLastError();
-  }
-  // HumanoidStandup: the Humanoid system lying down, 22 ground rows (F_R2)
-  if (fold && L == 16 && (k == BX_ENV_HUMANOID || k == BX_ENV_HUMANOID_STANDUP) &&
-      feat == (F_SPH | F_G1 | F_R2)) {
-    if (a.packed && a.n_steps <= 1)
-      launch_one<EnvArgs>(env_step_packed_kernel<16, 1, F_SPH | F_G1 | F_R2, 8, EK_HUM>, grid, tpb, lds, s, a);
-    else
-      launch_one<EnvArgs>(env_step_kernel<16, 1, F_SPH | F_G1 | F_R2, 8, EK_HUM>, grid, tpb, lds, s, a);
-    return hipGetLastError();
-  }
-  // every other env's Env.step (one packed step): the one-step kernels, whose
-  // first loads need no header
-  if (a.packed && a.n_steps <= 1) {
-    BX_DISPATCH_SINGLE(env_step_packed_kernel, EnvArgs)
-    return hipGetLastError();
-  }
-  BX_DISPATCH_SINGLE(env_step_kernel, EnvArgs)
-  return hipGetLastError();
-}
-// the joint halves' partner exchange alone (bx_debug_partner)
-__global__ void __launch_bounds__(64) partner_kernel(float* out, int lanes) {
-  const float v = (float)threadIdx.x;
-  out[threadIdx.x] = lanes == 16 ? xh(v) : v;
-}
-hipError_t debug_partner(float* out64, int lanes, hipStream_t s) {
-  hipLaunchKernelGGL(partner_kernel, dim3(1), dim3(64), 0, s, out64, lanes);
-  return hipGetLastError();
-}
-hipError_t debug_stamps(unsigned long long* out, int reset) {
-#ifdef BX_STAMPS
-  static unsigned long long host[4096][16];
-  hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(bx_stamp_wave), sizeof(host));
-  if (reset & 4) {  // the per-workgroup sums themselves (4096 x 16)
-    memcpy(out, host, sizeof(host));
-    return e;
-  }
-  for (int k = 0; k < 16; k++) {
-    out[k] = 0;
-    for (int w = 0; w < 4096; w++) out[k] += host[w][k];
-  }
-  if (e == hipSuccess && reset) {
-    memset(host, 0, sizeof(host));
-    e = hipMemcpyToSymbol(HIP_SYMBOL(bx_stamp_wave), host, sizeof(host));
-  }
-  return e;
-#else
-  (void)out;
-  (void)reset;
-  return hipErrorNotSupported;
-#endif
-}
-#else
-hipError_t launch_system_step_generic(int L, int mode, int feat, int tpb, int64_t n_envs, size_t lds,
-                                      hipStream_t s, const StepArgs& a) {
-  const int epb = tpb / L;
-  dim3 grid((unsigned)((n_envs + epb - 1) / epb));
-  BX_DISPATCH_GENERIC(system_step_kernel, StepArgs)
-  return hipGetLastError();
-}
-hipError_t launch_env_step_generic(int L, int mode, int feat, int tpb, int64_t n_envs, size_t lds,
-                                   hipStream_t s, const EnvArgs& a) {
-  const int epb = tpb / L;
-  dim3 grid((unsigned)((n_envs + epb - 1) / epb));
-  BX_DISPATCH_GENERIC(env_step_kernel, EnvArgs)
-  return hipGetLastError();
-}
-hipError_t launch_system_step_multi(int L, int jh, int64_t n_envs, size_t lds, hipStream_t s,
-                                    const StepArgs& a) {
-  dim3 grid((unsigned)n_envs);
-  switch (L * 2 + (jh ? 1 : 0)) {
-    case 128 * 2: launch_one<StepArgs>(system_step_multi_kernel<128>, grid, 128, lds, s, a); break;
-    case 128 * 2 + 1: launch_one<StepArgs>(system_step_multi_kernel<128, F_JH>, grid, 128, lds, s, a); break;
-    case 256 * 2: launch_one<StepArgs>(system_step_multi_kernel<256>, grid, 256, lds, s, a); break;
-    case 256 * 2 + 1: launch_one<StepArgs>(system_step_multi_kernel<256, F_JH>, grid, 256, lds, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-hipError_t launch_info_obs(int L, int64_t n_envs, size_t lds, hipStream_t s, const InfoArgs& a) {
-  int epb = L > 64 ? 1 : 64 / L;
-  dim3 grid((unsigned)((n_envs + epb - 1) / epb));
-  if (L == 128) { if (lds > 65536) (void)hipFuncSetAttribute((const void*)info_obs_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); hipLaunchKernelGGL(info_obs_kernel<128>, grid, dim3(128), lds, s, a); }
-  else if (L == 256) { if (lds > 65536) (void)hipFuncSetAttribute((const void*)info_obs_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); hipLaunchKernelGGL(info_obs_kernel<256>, grid, dim3(256), lds, s, a); }
-  else if (L == 16) { if (lds > 65536) (void)hipFuncSetAttribute((const void*)info_obs_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); hipLaunchKernelGGL(info_obs_kernel<16>, grid, dim3(64), lds, s, a); }
-  else if (L == 32) { if (lds > 65536) (void)hipFuncSetAttribute((const void*)info_obs_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); hipLaunchKernelGGL(info_obs_kernel<32>, grid, dim3(64), lds, s, a); }
-  else { if (lds > 65536) (void)hipFuncSetAttribute((const void*)info_obs_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); hipLaunchKernelGGL(info_obs_kernel<64>, grid, dim3(64), lds, s, a); }
-  return hipGetLastError();
-}
-hipError_t debug_mstamps(unsigned long long* out, int reset) {
-#ifdef BX_MSTAMPS
-  static unsigned long long host[4096][16];
-  hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(bx_mstamp_wave), sizeof(host));
-  for (int k = 0; k < 16; k++) {
-    out[k] = 0;
-    for (int w = 0; w < 4096; w++) out[k] += host[w][k];
-  }
-  if (e == hipSuccess && reset) {
-    memset(host, 0, sizeof(host));
-    e = hipMemcpyToSymbol(HIP_SYMBOL(bx_mstamp_wave), host, sizeof(host));
-  }
-  return e;
-#else
-  (void)out;
-  (void)reset;
-  return hipErrorNotSupported;
-#endif
-}
-hipError_t launch_default_qp(int64_t n_envs, size_t lds, hipStream_t s, const ResetArgs& a) {
-  dim3 grid((unsigned)((n_envs + 63) / 64));
-  if (lds > 65536) (void)hipFuncSetAttribute((const void*)default_qp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(default_qp_kernel, grid, dim3(64), lds, s, a);
-  return hipGetLastError();
-}
-hipError_t launch_uniform(float* out, int64_t n, uint64_t seed, uint64_t offset, float lo, float hi,
-                          hipStream_t s) {
-  dim3 grid((unsigned)((n + 255) / 256));
-  hipLaunchKernelGGL(uniform_kernel, grid, dim3(256), 0, s, out, n, seed, offset, lo, hi);
-  return hipGetLastError();
-}
-hipError_t launch_uniform_slabs(float* out, int64_t slab_n, int64_t n_slabs, uint64_t seed,
-                                uint64_t offset, uint64_t slab_stride, const int64_t* epoch,
-                                uint64_t epoch_stride, float lo, float hi, hipStream_t s) {
-  const int64_t n = slab_n * n_slabs;
-  dim3 grid((unsigned)((n + 255) / 256));
-  hipLaunchKernelGGL(uniform_slabs_kernel, grid, dim3(256), 0, s, out, slab_n, n, seed, offset,
-                     slab_stride, epoch, epoch_stride, lo, hi);
-  return hipGetLastError();
-}
-
-#endif  // BX_TU_FAST
 
 }  // namespace bx

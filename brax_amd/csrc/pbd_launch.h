@@ -1,4 +1,5 @@
-// pbd_launch.h — host-side launch entry points of pbd_kernels.hip
+// pbd_launch.h — host-side launch entry points of pbd_single.hip,
+// pbd_generic.hip and phase_kernels.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -89,6 +90,15 @@ struct ResetArgs {
   uint32_t* rng_out;  // UR5E / FETCH / GRASP: the per-env streams (or null)
 };
 
+// one kernel launch (the translation units' launchers)
+template <typename Args>
+static void launch_one(void (*k)(Args), dim3 grid, int tpb, size_t lds, hipStream_t s, const Args& a) {
+  // tpb threads per workgroup (a multiple of L, <= 64): 64 / L envs share a
+  // wavefront by default; 32 halves that (twice the waves for one batch)
+  if (lds > 65536) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(k, grid, dim3(tpb), lds, s, a);
+}
+
 // SINGLE-mode step kernels (fast-reciprocal translation unit)
 hipError_t launch_system_step_single(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
                                      hipStream_t s, const StepArgs& a);
@@ -113,9 +123,9 @@ hipError_t launch_uniform_slabs(float* out, int64_t slab_n, int64_t n_slabs, uin
 
 hipError_t debug_stamps(unsigned long long* out, int reset);
 hipError_t debug_partner(float* out64, int lanes, hipStream_t s);
-// the feature mask F of the SINGLE-mode kernel BX_DISPATCH_SINGLE picks for
-// (lanes, system features, gather width): its bit 1 (F_SPH) says whether it
-// reads the LDS-staged joint limit rows
+// the feature mask F of the SINGLE-mode kernel single_variant (pbd_dispatch.h)
+// picks for (lanes, system features, gather width): its bit 1 (F_SPH) says
+// whether it reads the LDS-staged joint limit rows
 int single_kernel_feat(int L, int feat, int gw);
 hipError_t debug_mstamps(unsigned long long* out, int reset);  // MULTI mode (item-loop TU)
 hipError_t launch_phase(int which, const uint32_t* blob, int N, int64_t B, int64_t plane,

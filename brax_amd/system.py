@@ -178,7 +178,7 @@ class System:
     per_wg = lds.value
     envs_per_wg = max(64 // lanes.value, 1)
     by_lds = (160 * 1024 // per_wg) * envs_per_wg if per_wg else None
-    # system_step_multi_kernel<L>: amdgpu_waves_per_eu(2) (pbd_kernels.hip):
+    # system_step_multi_kernel<L>: amdgpu_waves_per_eu(2) (pbd_generic.hip):
     # 256 registers, two waves per SIMD, eight per CU, L / 64 per env
     by_regs = 8 // (lanes.value // 64) if mode.value == 3 else None
     runs = min(x for x in (by_lds, by_regs) if x is not None) if (by_lds or by_regs) else None

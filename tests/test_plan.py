@@ -23,7 +23,7 @@ def test_ant_mountain4_runs_four_envs_per_cu(cutoff):
   threads per env (two waves). The kernel is built for two waves per SIMD
   (256 registers), so the register file holds four such envs per CU, and
   since round 6 the LDS does too: only the penetrating rows get contact
-  slots (64 per chunk) and a contact record (128 in LDS), the rows' bounds
+  slots (128 per chunk) and a contact record (128 in LDS), the rows' bounds
   are 12 bytes, and the Info accumulators, the NearNeighbors ranks / lists
   and the near-row list share words that are dead while they live, so an
   env's tail fits 40 KB with all pairs (cutoff 0) and culled (cutoff 36)."""

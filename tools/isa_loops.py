@@ -1,6 +1,6 @@
 """Static instruction mix of one kernel's ISA per loop depth (diagnostic).
 
-  hipcc ... --cuda-device-only -S pbd_kernels.hip -o single.s
+  hipcc ... --cuda-device-only -S pbd_single.hip -o single.s
   python tools/isa_loops.py single.s '_ZN2bx15env_step_kernelILi16ELi1ELi0ELi4E'
 
 Counts VALU, LDS, waitcnt, SGPR-spill lane moves and scratch accesses by the

@@ -3,8 +3,8 @@
 Build the SINGLE-mode translation unit's assembly with the phase marks (the
 stamp points as `;BXPHASE k` comments, code not scheduled across them):
 
-  cd brax_amd/csrc && hipcc <the Makefile's CXXFLAGS + SCHED> -DBX_TU_FAST \
-      -DBX_PHASE_MARKS --cuda-device-only -S pbd_kernels.hip -o single_marks.s
+  cd brax_amd/csrc && hipcc <the Makefile's CXXFLAGS + SCHED> \
+      -DBX_PHASE_MARKS --cuda-device-only -S pbd_single.hip -o single_marks.s
   python tools/phase_mix.py single_marks.s <mangled kernel name> [--json out]
 
 Every instruction is attributed to the phase whose mark ENDS its stretch of
