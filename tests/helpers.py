@@ -198,6 +198,44 @@ def set_variant(sys_, variant):
   return lib.bx_system_set_variant(sys_._h, 256, 0)
 
 
+def piled_mountain4(cutoff, substeps):
+  """Ant Mountain(4) with its four ants piled onto one spot: (cfg, qp0), the
+  config with `collider_cutoff` / `substeps` set and a start state (N, 13)
+  pos|rot|vel|ang rounded to fp32. From the float64 oracle's default_qp with
+  zero joint angles and velocities, every body of cloned ant i (the bodies
+  named `*_i`, i in 0..2) is translated so that its torso sits 2 cm from ant
+  0's: at torso0 + 0.02 (cos 2.1 k, sin 2.1 k, 0.6 k), k = i + 1. Rotations
+  and velocities stay. Its first collision pass lists more penetrating rows
+  than the MULTI kernel's LDS contact buffer holds (pbd_layout.h MCBUF), all
+  finite (tests/test_gpu_multi_overflow.py; the counts are pinned on the CPU
+  there)."""
+  from oracle import oracle
+  cfg = config_for('mountain4')
+  cfg.collider_cutoff = cutoff
+  cfg.substeps = substeps
+  vc, d, meta = compiler.compile_system(cfg)
+  o = oracle.Oracle(d, compiler.compile_reset(vc, meta['body_index']), np.float64)
+  z = np.zeros((1, meta['num_joint_dof']))
+  qp = o.default_qp(z, z)[0]
+  bi = meta['body_index']
+  torso0 = qp[bi['$ Torso'], 0:3].copy()
+  for i in range(3):
+    k = i + 1
+    shift = (torso0 + 0.02 * np.array([np.cos(2.1 * k), np.sin(2.1 * k), 0.6 * k])
+             - qp[bi[f'$ Torso_{i}'], 0:3])
+    for name, b in bi.items():
+      if name.endswith(f'_{i}'):
+        qp[b, 0:3] += shift
+  return cfg, qp.astype(np.float32)
+
+
+def piled_actions(B, steps):
+  """The piled scene's actions: env e's action at step t is row e of the t-th
+  (B, 32) draw of default_rng(5).uniform(-1, 1), rounded to fp32."""
+  rng = np.random.default_rng(5)
+  return [rng.uniform(-1, 1, (B, 32)).astype(np.float32) for _ in range(steps)]
+
+
 def normwise(a, b):
   """Per-env normwise error max|a-b| / max(1, max|b|) over trailing axes."""
   a = np.asarray(a, np.float64)
