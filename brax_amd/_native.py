@@ -82,6 +82,13 @@ _SIGS = {
                           C.c_uint64, C.c_float, C.c_float, C.c_void_p], C.c_int),
     'bx_uniform_slabs': ([C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64,
                           C.c_void_p, C.c_uint64, C.c_float, C.c_float, C.c_void_p], C.c_int),
+    'bx_normal_slabs': ([C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64,
+                         C.c_void_p, C.c_uint64, C.c_void_p], C.c_int),
+    'bx_env_rollout_policy': ([C.c_void_p, C.POINTER(abi.BxEnvParams), C.c_int64, C.c_int32,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.POINTER(abi.BxPolicy), C.c_uint64, C.c_uint64, C.c_uint64,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p], C.c_int),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -12,7 +12,7 @@ i32p = C.POINTER(C.c_int32)
 f64p = C.POINTER(C.c_double)
 f32p = C.POINTER(C.c_float)
 
-ABI_VERSION = 13  # include/brax_amd.h BX_ABI_VERSION
+ABI_VERSION = 14  # include/brax_amd.h BX_ABI_VERSION
 
 _DESC_FIELDS = [
     ('n_bodies', C.c_int32), ('n_joints', C.c_int32), ('n_actuators', C.c_int32),
@@ -96,6 +96,17 @@ class BxEnvParams(C.Structure):
               ('action_repeat', C.c_int32), ('auto_reset', C.c_int32),
               ('obs_flags', C.c_int32), ('coef', C.c_float * 8),
               ('first_qp', BxQP), ('first_obs', C.c_void_p), ('act_map', C.c_void_p)]
+
+
+POLICY_MAX_LAYERS, POLICY_MAX_WIDTH, POLICY_MAX_OBS = 8, 128, 512  # BX_POLICY_MAX_*
+POLICY_ACTIVATIONS = {'swish': 0, 'relu': 1, 'tanh': 2}  # BX_POLICY_SWISH / RELU / TANH
+
+
+class BxPolicy(C.Structure):
+  _fields_ = [('params', C.c_void_p), ('n_layers', C.c_int32),
+              ('width', C.c_int32 * POLICY_MAX_LAYERS), ('activation', C.c_int32),
+              ('obs_mean', C.c_void_p), ('obs_std', C.c_void_p), ('min_std', C.c_float),
+              ('deterministic', C.c_int32), ('action_size', C.c_int32)]
 
 
 def _arr(x, dtype):

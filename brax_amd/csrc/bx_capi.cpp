@@ -1320,13 +1320,14 @@ static int env_step_impl(bx_system* S, const bx_env_params* env, int64_t n_envs,
                          const bx_env_state* in, const float* act, int64_t act_stride,
                          int64_t act_width, const bx_env_state* out, void* stream,
                          int32_t n_steps, int64_t act_step, int64_t out_step, int64_t rng_step,
-                         const DrawSpec* draw = nullptr, bool packed = false) {
+                         const DrawSpec* draw = nullptr, bool packed = false,
+                         const PolArgs* pol = nullptr, size_t pol_lds = 0) {
   if (!S || !env || !in || !out) return fail("null argument");
   DEVICE_SCOPE(S);
   if (check_env(S, env)) return 1;
   // an empty batch is a no-op (its buffers, the action included, may be null)
   if (n_envs <= 0) return n_envs == 0 ? 0 : fail("negative n_envs");
-  if (draw ? check_draw(S, env, act_width) : check_act(S, act, act_stride, act_width)) return 1;
+  if ((draw || pol) ? check_draw(S, env, act_width) : check_act(S, act, act_stride, act_width)) return 1;
   if (!qp_ok(in->qp) || !qp_ok(out->qp)) return fail("null qp field");
   if (!in->done || !out->done || !out->reward || !out->obs) return fail("null env buffer");
   if (env->auto_reset && (!qp_ok(env->first_qp) || !env->first_obs))
@@ -1364,7 +1365,10 @@ static int env_step_impl(bx_system* S, const bx_env_params* env, int64_t n_envs,
     a.draw_hi = draw->hi;
     a.act_out = draw->act_out;
   }
-  if (S->mode == 1)
+  if (pol)  // (policy_plan admits SINGLE-mode systems only)
+    HIP_OK(launch_env_policy_single(S->L, S->feat, S->gw, S->tpb, n_envs, pol_lds, as_stream(stream), a,
+                                    *pol, S->fold ? (1 | (S->jb ? 2 : 0)) : 0));
+  else if (S->mode == 1)
     HIP_OK(launch_env_step_single(S->L, S->feat, S->gw, S->tpb, n_envs, step_lds(S), as_stream(stream), a,
                                   S->fold ? (1 | (S->jb ? 2 : 0)) : 0));
   else if (S->mode == 3)  // MULTI-mode systems step envs with the item-loop kernel
@@ -1385,7 +1389,8 @@ static int env_step_packed(bx_system* S, const bx_env_params* env, int64_t n_env
                            const float* qp_in, const float* done_in, const float* steps_in,
                            const uint32_t* rng_in, const float* act, int64_t act_stride,
                            int64_t act_step, int64_t act_width, float* out, uint32_t* rng_out,
-                           void* stream, const DrawSpec* draw = nullptr) {
+                           void* stream, const DrawSpec* draw = nullptr,
+                           const PolArgs* pol = nullptr, size_t pol_lds = 0) {
   if (!S || !env) return fail("null argument");
   if (n_envs <= 0) {
     if (check_env(S, env)) return 1;
@@ -1421,7 +1426,7 @@ static int env_step_packed(bx_system* S, const bx_env_params* env, int64_t n_env
   // one step's output block: qp | obs | reward, done, steps, truncation | metrics
   const int64_t block = B * (N * 16 + env->obs_size + 4 + env->n_metrics);
   return env_step_impl(S, env, n_envs, &in, act, act_stride, act_width, &o, stream, n_steps,
-                       act_step, block, B, draw, true);
+                       act_step, block, B, draw, true, pol, pol_lds);
 }
 
 int bx_env_step_packed(bx_system* S, const bx_env_params* env, int64_t n_envs,
@@ -1456,6 +1461,85 @@ int bx_env_rollout_random(bx_system* S, const bx_env_params* env, int64_t n_envs
   const DrawSpec d{seed, offset, step_stride, lo, hi, act_out};
   return env_step_packed(S, env, n_envs, n_steps, qp_in, done_in, steps_in, rng_in, nullptr, 0, 0,
                          act_width, out, rng_out, stream, &d);
+}
+
+// bx_env_rollout_policy's descriptor checked against its limits and laid out
+// in the workgroup's LDS past the envs' areas: Q's shape fields and *lds (the
+// launch's dynamic LDS); the parameters are staged while the workgroup stays
+// within a quarter of the compute unit's 160 KiB (the 4,096-env launch's four
+// one-wave workgroups per compute unit stay co-resident)
+static int policy_plan(const bx_system* S, const bx_env_params* env, const bx_policy* p,
+                       int64_t act_width, PolArgs* Q, size_t* lds) {
+  if (!p) return fail("null policy");
+  if (S->mode != 1) return fail("the policy rollout needs a SINGLE-mode system");
+  if (!p->params || ((uintptr_t)p->params & 15)) return fail("policy parameters: null or not 16-byte aligned");
+  if (p->n_layers < 1 || p->n_layers > BX_POLICY_MAX_LAYERS)
+    return fail("policy: 1.." + std::to_string(BX_POLICY_MAX_LAYERS) + " layers");
+  if (p->activation != BX_POLICY_SWISH && p->activation != BX_POLICY_RELU && p->activation != BX_POLICY_TANH)
+    return fail("policy: unknown activation");
+  if ((p->obs_mean == nullptr) != (p->obs_std == nullptr)) return fail("policy: obs_mean and obs_std go together");
+  if (env->obs_size < 1 || env->obs_size > BX_POLICY_MAX_OBS)
+    return fail("policy: obs_size beyond " + std::to_string(BX_POLICY_MAX_OBS));
+  if (!(p->min_std >= 0.f)) return fail("policy: negative min_std");
+  const int A = (int)act_width;
+  int64_t np = 0;
+  int wmax = std::max(env->obs_size, 2 * A);
+  Q->width[0] = env->obs_size;
+  for (int l = 0; l < p->n_layers; l++) {
+    const int w = p->width[l];
+    if (w < 1 || w > BX_POLICY_MAX_WIDTH)
+      return fail("policy: layer widths 1.." + std::to_string(BX_POLICY_MAX_WIDTH));
+    np += (int64_t)(Q->width[l] + 1) * w;
+    Q->width[l + 1] = w;
+    wmax = std::max(wmax, w);
+  }
+  const int last = p->width[p->n_layers - 1];
+  if (last != 2 * A && !(last == A && p->deterministic))
+    return fail("policy: the last layer is 2 x action_size wide (action_size when deterministic)");
+  Q->params = p->params;
+  Q->mean = p->obs_mean;
+  Q->std = p->obs_std;
+  Q->n_layers = p->n_layers;
+  Q->act_fn = p->activation;
+  Q->det = p->deterministic ? 1 : 0;
+  Q->min_std = p->min_std;
+  Q->n_params = (int32_t)np;
+  Q->obs_words = (env->obs_size + 3) & ~3;
+  Q->buf_words = (wmax + 3) & ~3;
+  const size_t base = (step_lds(S) + 15) & ~(size_t)15;
+  const size_t envs = (size_t)(S->tpb / S->L) * (Q->obs_words + 2 * Q->buf_words) * 4;
+  const size_t staged = (size_t)((np + 3) & ~(int64_t)3) * 4;
+  Q->lds_off = (int32_t)(base / 4);
+  Q->stage = base + envs + staged <= 40 * 1024 ? 1 : 0;
+  *lds = base + envs + (Q->stage ? staged : 0);
+  if (*lds > 160 * 1024) return fail("policy: the workgroup's LDS exceeds 160 KiB");
+  return 0;
+}
+
+int bx_env_rollout_policy(bx_system* S, const bx_env_params* env, int64_t n_envs, int32_t n_steps,
+                          const float* qp_in, const float* obs_in, const float* done_in,
+                          const float* steps_in, const uint32_t* rng_in, const bx_policy* policy,
+                          uint64_t seed, uint64_t offset, uint64_t step_stride, float* act_out,
+                          float* raw_out, float* logp_out, float* out, uint32_t* rng_out,
+                          void* stream) {
+  if (!S || !env) return fail("null argument");
+  if (n_steps < 0) return fail("negative n_steps");
+  if (!policy) return fail("null policy");
+  const int64_t A = policy->action_size;
+  PolArgs q{};
+  size_t lds = 0;
+  if (check_env(S, env) || check_draw(S, env, A) || policy_plan(S, env, policy, A, &q, &lds)) return 1;
+  if (n_steps == 0) return 0;
+  if (n_envs > 0 && !obs_in) return fail("null obs_in");
+  q.obs_in = obs_in;
+  q.raw_out = raw_out;
+  q.logp_out = logp_out;
+  q.seed = seed;
+  q.offset = offset;
+  q.step = step_stride;
+  const DrawSpec d{0, 0, 0, 0.f, 0.f, act_out};
+  return env_step_packed(S, env, n_envs, n_steps, qp_in, done_in, steps_in, rng_in, nullptr, 0, 0,
+                         A, out, rng_out, stream, &d, &q, lds);
 }
 
 int bx_system_info(bx_system* S, int64_t n_envs, const bx_qp* qp, const bx_info* info, void* stream) {
@@ -1676,6 +1760,23 @@ int bx_uniform_slabs(float* out, int64_t slab_n, int64_t n_slabs, uint64_t seed,
   if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
   HIP_OK(launch_uniform_slabs(out, slab_n, n_slabs, seed, offset, slab_stride, epoch, epoch_stride,
                               lo, hi, st));
+  return 0;
+}
+
+int bx_normal_slabs(float* out, int64_t slab_n, int64_t n_slabs, uint64_t seed, uint64_t offset,
+                    uint64_t slab_stride, const int64_t* epoch, uint64_t epoch_stride, void* stream) {
+  if (slab_n < 0 || n_slabs < 0) return fail("negative size");
+  if (slab_n == 0 || n_slabs == 0) return 0;
+  if (slab_n > INT64_MAX / n_slabs || slab_n * n_slabs > ((int64_t)1 << 40))
+    return fail("too many elements for one draw");
+  if (!out) return fail("null output");
+  int dev = -1;
+  hipStream_t st = as_stream(stream);
+  if (st) HIP_OK(hipStreamGetDevice(st, &dev));
+  else HIP_OK(hipGetDevice(&dev));
+  DeviceScope scope(dev);
+  if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
+  HIP_OK(launch_normal_slabs(out, slab_n, n_slabs, seed, offset, slab_stride, epoch, epoch_stride, st));
   return 0;
 }
 

@@ -4491,6 +4491,120 @@ __global__ void __launch_bounds__(L > 64 ? L : 64) BX_STEP_ATTR system_step_kern
 
 
 
+// ---------------------------------------------------------------------------
+// the policy action source (env_policy_rollout kernels): networks.MLP,
+// NormalTanhDistribution and make_inference_fn (training/distribution.py:
+// 94-158, ppo/networks.py:62-88) evaluated per env from its observation row
+// in LDS. NaN: the build assumes none, so every select / max / library call
+// that could swallow one is bypassed through is_nan (opaque): a non-finite
+// observation gives a non-finite action, as jnp does.
+// ---------------------------------------------------------------------------
+// the standard normal of counters (i, i + 1): Box-Muller's cosine branch,
+// sqrt(-2 ln(1 - U_i)) cos(2 pi U_{i+1}) (1 - U in (0, 1]); the asm pins the
+// product's rounding, so bx_normal_slabs and the kernels write the same bits
+__device__ __forceinline__ float normal_at(uint64_t seed, uint64_t i) {
+  const float u0 = uniform_at(seed, i, 0.f, 1.f), u1 = uniform_at(seed, i + 1, 0.f, 1.f);
+  float r = sqrtf(-2.f * logf(1.f - u0));
+  float c = cosf(6.28318530717958647692f * u1);
+  asm("" : "+v"(r));
+  asm("" : "+v"(c));
+  float n = r * c;
+  asm("" : "+v"(n));
+  return n;
+}
+__device__ __forceinline__ float pol_tanh(float x) { return is_nan(x) ? x : tanhf(x); }
+// jax.nn.softplus = logaddexp(x, 0) = max(x, 0) + log1p(exp(-|x|))
+__device__ __forceinline__ float pol_softplus(float x) {
+  const float r = fmaxf(x, 0.f) + log1pf(expf(-fabsf(x)));
+  return is_nan(x) ? x : r;
+}
+__device__ __forceinline__ float pol_act(float x, int fn) {
+  if (fn == BX_POLICY_RELU) return is_nan(x) ? x : fmaxf(x, 0.f);
+  if (fn == BX_POLICY_TANH) return pol_tanh(x);
+  // swish: x sigmoid(x) (exp(-x) = inf for very negative x: -0)
+  const float r = x / (1.f + expf(-x));
+  return is_nan(x) ? x : r;
+}
+// one dense layer over the env's L lanes: output unit j on lane j % L, the
+// input activations broadcast from LDS, W (n_in, n_out) row-major (the lanes'
+// reads of a row are consecutive, and the same for every env of the wave)
+template <int L>
+__device__ __forceinline__ void pol_layer(const float* W, const float* hin, float* hout, int n_in,
+                                          int n_out, int lane, int fn) {
+  const float* b = W + n_in * n_out;
+  for (int j = lane; j < n_out; j += L) {
+    float s0 = b[j], s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    const float* w = W + j;
+    int i = 0;
+    // (unrolled: 16 weight loads in flight per trip; with one wave per SIMD
+    // the layer runs at the loads' latency, most of all when they are global)
+#pragma unroll 4
+    for (; i + 4 <= n_in; i += 4) {
+      const f32x4 h = ld4a(hin + i);
+      s0 = fmaf(h.x, w[(i + 0) * n_out], s0);
+      s1 = fmaf(h.y, w[(i + 1) * n_out], s1);
+      s2 = fmaf(h.z, w[(i + 2) * n_out], s2);
+      s3 = fmaf(h.w, w[(i + 3) * n_out], s3);
+    }
+    for (; i < n_in; i++) s0 = fmaf(hin[i], w[i * n_out], s0);
+    const float s = (s0 + s1) + (s2 + s3);
+    hout[j] = fn < 0 ? s : pol_act(s, fn);
+  }
+}
+// step t's action row of env e (el: e, or 0 past the batch) from its
+// observation row pobs: the actions into the returned buffer's first aw words
+// (every lane of the env calls; the caller fences before reading them)
+template <int L>
+__device__ __forceinline__ float* policy_eval(const PolArgs& Q, const float* W, const float* pobs,
+                                              float* b0, float* b1, int lane, int64_t el, int64_t e,
+                                              bool valid, int t, int aw, int64_t n_envs) {
+  const float* hin = pobs;
+  if (Q.mean) {
+    for (int i = lane; i < Q.width[0]; i += L) {
+      const float o = pobs[i];
+      const float r = (o - Q.mean[i]) / Q.std[i];
+      b0[i] = is_nan(o) ? o : r;
+    }
+    hin = b0;
+    esync<L>();
+  }
+  float* hout = hin == b0 ? b1 : b0;
+  for (int l = 0; l < Q.n_layers; l++) {
+    const int n_in = Q.width[l], n_out = Q.width[l + 1];
+    pol_layer<L>(W, hin, hout, n_in, n_out, lane, l + 1 < Q.n_layers ? Q.act_fn : -1);
+    W += (n_in + 1) * n_out;
+    esync<L>();
+    hin = hout;
+    hout = hin == b0 ? b1 : b0;
+  }
+  // the head: hin holds the logits (loc | scale parameter), hout takes the
+  // actions (0..aw) and the log-prob terms (aw..2 aw)
+  const bool has_scale = Q.width[Q.n_layers] >= 2 * aw;
+  for (int a = lane; a < aw; a += L) {
+    const float loc = hin[a];
+    float scale = 1.f, eps = 0.f;
+    if (has_scale) scale = pol_softplus(hin[aw + a]) + Q.min_std;
+    if (!Q.det)
+      eps = normal_at(Q.seed, Q.offset + (uint64_t)t * Q.step + ((uint64_t)el * (uint64_t)aw + (uint64_t)a) * 2u);
+    const float raw = Q.det ? loc : fmaf(scale, eps, loc);
+    const float act = pol_tanh(raw);
+    // Normal.log_prob at raw ((raw - loc) / scale = eps; deterministic: the
+    // mode's, eps = 0) minus TanhBijector.forward_log_det_jacobian
+    const float lp = -0.5f * eps * eps - 0.91893853320467274178f - logf(scale) -
+                     2.f * (0.69314718055994530942f - raw - pol_softplus(-2.f * raw));
+    hout[a] = act;
+    hout[aw + a] = lp;
+    if (valid && Q.raw_out) Q.raw_out[((int64_t)t * n_envs + e) * aw + a] = raw;
+  }
+  esync<L>();
+  if (lane == 0 && valid && Q.logp_out) {
+    float s = 0.f;
+    for (int a = 0; a < aw; a++) s += hout[aw + a];
+    Q.logp_out[(int64_t)t * n_envs + e] = s;
+  }
+  return hout;
+}
+
 // Env.step fused with EpisodeWrapper/AutoResetWrapper (wrappers.py:105-148),
 // for A.n_steps consecutive steps (bx_env_rollout_packed; 1 for bx_env_step):
 // step t reads its action rows at act + t * act_step and writes its outputs at
@@ -4506,8 +4620,14 @@ __global__ void __launch_bounds__(L > 64 ? L : 64) BX_STEP_ATTR system_step_kern
 // across the step loop (uniform registers the kernel otherwise spills)
 // ONE (env_step_packed_kernel, launched for n_steps <= 1 only): one step,
 // its first loads issued from the kernel arguments (EARLY below)
-template <int L, int MODE, int F, int M, int EK = EK_ANY, bool PK = false, bool ONE = false>
-__device__ __forceinline__ void env_step_body(const EnvArgs& A) {
+// POL (the env_policy_rollout kernels, pbd_policy.hip): step t's action row is
+// the policy Q's, evaluated from the env's observation row, which stays in
+// LDS: step 0 loads it from Q.obs_in, env_observe writes it there, the
+// AutoReset select overwrites it with first_obs, and each step copies it to
+// its output block
+template <int L, int MODE, int F, int M, int EK = EK_ANY, bool PK = false, bool ONE = false,
+          bool POL = false>
+__device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q = PolArgs{}) {
   BX_KSTAMP_DECL
   extern __shared__ __attribute__((aligned(16))) float smem[];
   // the packed SINGLE-mode kernels (Env.step's bx_env_step_packed, the
@@ -4592,7 +4712,7 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A) {
   constexpr int C = L < 64 ? L : 64;  // action-row chunk: one element per lane
   // on-device draws: the action row from the counter RNG, staged in LDS whole
   // (the host checks act_width <= act_read)
-  const bool drw = A.draw != 0;
+  const bool drw = POL || A.draw != 0;
   auto draw_at = [&](int t, int i) {
     return uniform_at(A.draw_seed,
                       A.draw_offset + (uint64_t)t * A.draw_step + (uint64_t)el * (uint64_t)aw + (uint64_t)i,
@@ -4600,7 +4720,26 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A) {
   };
   const float* arow_g = drw ? nullptr : A.act + el * A.act_stride;
   float a0 = 0.f;
-  if (aw > 0 && lane < C) a0 = drw ? draw_at(0, lane < aw ? lane : aw - 1) : (EARLY ? ea0 : arow_g[lane < aw ? lane : aw - 1]);
+  // POL: the staged parameters, the env's observation row and activation
+  // buffers (past every env's area)
+  const float* pw = nullptr;
+  float *pobs = nullptr, *pb0 = nullptr, *pb1 = nullptr, *pact = nullptr;
+  if constexpr (POL) {
+    float* pa = smem + Q.lds_off;
+    pw = Q.params;
+    if (Q.stage) {
+      for (int i = threadIdx.x; i < Q.n_params; i += blockDim.x) pa[i] = Q.params[i];
+      pw = pa;
+      pa += (Q.n_params + 3) & ~3;
+      __syncthreads();
+    }
+    pobs = pa + le * (Q.obs_words + 2 * Q.buf_words);
+    pb0 = pobs + Q.obs_words;
+    pb1 = pb0 + Q.buf_words;
+    for (int i = lane; i < P.obs_size; i += L) pobs[i] = Q.obs_in[el * P.obs_size + i];
+    esync<L>();
+  }
+  if (!POL && aw > 0 && lane < C) a0 = drw ? draw_at(0, lane < aw ? lane : aw - 1) : (EARLY ? ea0 : arow_g[lane < aw ? lane : aw - 1]);
   BX_PSTAMP(7);
   if constexpr (S) {
     // N <= L: the lane's body
@@ -4637,7 +4776,10 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A) {
   // (draw mode: the env programs that read the raw row are refused on the
   // host; physics reads the staged row)
   const float* act = (valid && !drw) ? A.act + e * A.act_stride + t * A.act_step : nullptr;
-  if (t > 0) {
+  if constexpr (POL) {
+    pact = policy_eval<L>(Q, pw, pobs, pb0, pb1, lane, el, e, valid, t, aw, A.n_envs);
+    esync<L>();
+  } else if (t > 0) {
     if (drw) {
       if (aw > 0 && lane < C) a0 = draw_at(t, lane < aw ? lane : aw - 1);
     } else {
@@ -4690,7 +4832,9 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A) {
   for (int i0 = 0; i0 < aw; i0 += C) {
     const int i = i0 + lane;
     float v = a0;
-    if (i0 > 0 && lane < C)
+    if constexpr (POL) {
+      v = pact[i < aw ? i : aw - 1];
+    } else if (i0 > 0 && lane < C)
       v = drw ? draw_at(t, i < aw ? i : aw - 1) : ((EARLY && i0 == C) ? ea1 : arow_g[i < aw ? i : aw - 1]);
     if (i >= aw || !valid) v = 0.f;
     if (drw && A.act_out && valid && lane < C && i < aw) A.act_out[((int64_t)t * A.n_envs + e) * aw + i] = v;
@@ -4706,7 +4850,24 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A) {
       if (i < H.act_read) E.arow[i] = v;
     }
     esync<L>();
-    if (lane == 0) {
+    if (POL && lane == 0) {
+      // the open-loop kernels' rounding of this sum, spelled out: there the
+      // compiler contracts the first chunk as fma(r0, r0, r1 * r1) and chains
+      // the rest (every env_step / env_rollout instantiation, read from their
+      // assembly), here the step loop's accumulator would make it a plain
+      // chain from 0. The recorded actions replayed through `rollout` must
+      // give the same ctrl cost bit for bit (tests/test_gpu_policy_rollout.py)
+      if (i0 == 0) {
+        float r1 = E.red[1] * E.red[1];
+        asm("" : "+v"(r1));
+        sq = __builtin_fmaf(E.red[0], E.red[0], r1);
+#pragma unroll
+        for (int k = 2; k < C; k++) sq = __builtin_fmaf(E.red[k], E.red[k], sq);
+      } else {
+#pragma unroll
+        for (int k = 0; k < C; k++) sq = __builtin_fmaf(E.red[k], E.red[k], sq);
+      }
+    } else if (lane == 0) {
 #pragma unroll
       for (int k = 0; k < C; k++) sq += E.red[k] * E.red[k];
     }
@@ -4807,7 +4968,7 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A) {
     // (JB: the lane's hoisted body is its joint side's, not body lane)
     constexpr bool JBK = S && (F & F_JH) != 0 && EK != EK_ANY && (F & F_C16) == 0;
     env_observe<L, EK>(c, H, E, lane, kind, P.obs_flags, P.obs_size, act, aw,
-                   valid ? O.obs + e * P.obs_size : nullptr, P.coef, S ? &X.J : nullptr,
+                   valid ? (POL ? pobs : O.obs + e * P.obs_size) : nullptr, P.coef, S ? &X.J : nullptr,
                    (S && !JBK) ? &X.B : nullptr, (S && EK == EK_HUM) ? &X.A : nullptr);
     BX_KSTAMP(12);
     // the Ant kernel's contact cost: each body lane's clipped squares, summed
@@ -5056,9 +5217,15 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A) {
           for (int k = 0; k < 13; k++) s[k] = tmp[k];
         }
       }
-      for (int i = lane; i < P.obs_size; i += L) O.obs[e * P.obs_size + i] = P.first_obs[e * P.obs_size + i];
+      for (int i = lane; i < P.obs_size; i += L) {
+        const float fo = P.first_obs[e * P.obs_size + i];
+        O.obs[e * P.obs_size + i] = fo;
+        if constexpr (POL) pobs[i] = fo;
+      }
     } else {
       for (int b = lane; b < H.N; b += L) store_out_qp(b, E.qp + b * QP_STRIDE);
+      if constexpr (POL)
+        for (int i = lane; i < P.obs_size; i += L) O.obs[e * P.obs_size + i] = pobs[i];
     }
   }
   // the next step's input scalars: this step's outputs

@@ -50,6 +50,25 @@ struct EnvArgs {
   // from the blob
   BlobHdr hdr;
 };
+// the policy action source of the env_policy_rollout kernels
+// (bx_env_rollout_policy): step t's action row is an MLP of the env's current
+// observation, held in LDS between steps. The workgroup's policy area starts
+// lds_off words into its LDS: the staged parameters (stage != 0: n_params
+// words, padded to 4), then per env obs_words | buf_words | buf_words (the
+// observation row and two activation buffers)
+struct PolArgs {
+  const float* params;  // layer l: W (width[l], width[l+1]) row-major, then b (width[l+1])
+  const float* mean;    // (obs_size) or null
+  const float* std;
+  const float* obs_in;  // (B, obs_size): step 0's observation
+  float* raw_out;       // (K, B, A) or null
+  float* logp_out;      // (K, B) or null
+  int32_t n_layers, act_fn, det, stage;
+  int32_t width[BX_POLICY_MAX_LAYERS + 1];  // width[0] = obs_size
+  int32_t n_params, lds_off, obs_words, buf_words;
+  float min_std;
+  uint64_t seed, offset, step;
+};
 struct InfoArgs {
   const uint32_t* blob;
   int64_t n_envs;
@@ -104,6 +123,14 @@ hipError_t launch_system_step_single(int L, int feat, int gw, int tpb, int64_t n
                                      hipStream_t s, const StepArgs& a);
 hipError_t launch_env_step_single(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
                                   hipStream_t s, const EnvArgs& a, int fold);
+// the K-step rollout with the policy action source (pbd_policy.hip; SINGLE
+// mode only); policy_lds_budget: the largest per-workgroup LDS at which the
+// launch still stages the parameters
+hipError_t launch_env_policy_single(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
+                                    hipStream_t s, const EnvArgs& a, const PolArgs& q, int fold);
+hipError_t launch_normal_slabs(float* out, int64_t slab_n, int64_t n_slabs, uint64_t seed,
+                               uint64_t offset, uint64_t slab_stride, const int64_t* epoch,
+                               uint64_t epoch_stride, hipStream_t s);
 // MULTI-mode step kernel (large pbd scenes, L = 128 or 256 threads per env;
 // jh: the joint halves)
 hipError_t launch_system_step_multi(int L, int jh, int64_t n_envs, size_t lds, hipStream_t s,

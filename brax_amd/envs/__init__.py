@@ -17,6 +17,7 @@ from brax_amd.envs.tasks import Fetch, Grasp, Pusher, Reacher, ReacherAngle, Swi
 from brax_amd.envs.humanoid import Humanoid
 from brax_amd.envs.humanoid_standup import HumanoidStandup
 from brax_amd.envs.fast import Fast
+from brax_amd.envs.policy import MLPPolicy, PolicyExtras, policy_rollout
 
 _envs = {
     'acrobot': Acrobot,

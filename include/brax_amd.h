@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define BX_ABI_VERSION 13
+#define BX_ABI_VERSION 14
 
 /* joint kinds, actuator kinds, contact functions (descriptor enums) */
 enum { BX_JOINT_REVOLUTE = 1, BX_JOINT_UNIVERSAL = 2, BX_JOINT_SPHERICAL = 3 };
@@ -410,6 +410,64 @@ int bx_env_rollout_random(bx_system* sys, const bx_env_params* env, int64_t n_en
                           int64_t act_width, float* act_out, float* out, uint32_t* rng_out,
                           void* stream);
 
+/* An MLP policy with a NormalTanh head (the reference's networks.MLP,
+ * distribution.NormalTanhDistribution and ppo/networks.make_inference_fn) as
+ * a plain descriptor; every buffer is the caller's, on the system's device,
+ * and is read at launch time, so parameters updated in place (or a replayed
+ * graph) take effect without a new descriptor.
+ *   params: layer l's kernel W (width[l-1], width[l]) row-major (flax's
+ *     layout; width[-1] = obs_size), then its bias (width[l]), layer after
+ *     layer, float32, 16-byte aligned;
+ *   the last layer's width is 2 A (loc | scale parameter), or A with
+ *     deterministic set; hidden layers apply `activation`;
+ *   obs_mean / obs_std (obs_size each, both or neither): x = (obs - mean) / std;
+ *   scale = softplus(s) + min_std; raw = loc + scale * eps (loc when
+ *     deterministic); action = tanh(raw).
+ * Limits (beyond them the call fails, nothing is launched): 1..8 layers,
+ * widths 1..128, obs_size <= 512, and the workgroup's LDS (the system's
+ * bx_system_lds_bytes plus, per env of the workgroup, 4 * (obs_size + 2 *
+ * max(obs_size, widths, 2 A)) bytes rounded up to 16-byte records) within
+ * 160 KiB. The parameters are staged in LDS when that total plus 4 * n_params
+ * stays within 40 KiB (four workgroups co-resident per compute unit), else
+ * they are read from global memory through the cache (ABI 14). */
+#define BX_POLICY_MAX_LAYERS 8
+#define BX_POLICY_MAX_WIDTH 128
+#define BX_POLICY_MAX_OBS 512
+#define BX_POLICY_SWISH 0
+#define BX_POLICY_RELU 1
+#define BX_POLICY_TANH 2
+typedef struct bx_policy {
+  const float* params;
+  int32_t n_layers;
+  int32_t width[BX_POLICY_MAX_LAYERS];
+  int32_t activation; /* BX_POLICY_* */
+  const float* obs_mean;
+  const float* obs_std;
+  float min_std;
+  int32_t deterministic;
+  int32_t action_size; /* A: the env's action row (the system stages all of it) */
+} bx_policy;
+
+/* bx_env_rollout_packed with step t's actions computed inside the launch by
+ * `policy` from the env's current observation: step 0 reads obs_in (n_envs,
+ * obs_size), step t > 0 the observation step t - 1 wrote to its output block
+ * (after an AutoReset select: first_obs); the row stays on chip. The noise of
+ * step t, env e, action a is N(seed, i) = sqrt(-2 ln(1 - U(seed, i))) *
+ * cos(2 pi U(seed, i + 1)) with i = offset + t * step_stride + (e * A + a) * 2
+ * and U the [0, 1) draw of bx_uniform: the bits bx_normal_slabs(eps, B * A, K,
+ * seed, offset, step_stride, NULL, 0) writes. Optional outputs: act_out and
+ * raw_out (K, n_envs, A), logp_out (K, n_envs): log_prob of raw under the
+ * head's Normal minus the tanh log-det, summed over the actions
+ * (deterministic: evaluated at the mode, eps = 0). The env kinds
+ * bx_env_rollout_random refuses are refused here too, as are systems not in
+ * SINGLE mode. n_steps = 0 only checks the arguments (ABI 14). */
+int bx_env_rollout_policy(bx_system* sys, const bx_env_params* env, int64_t n_envs,
+                          int32_t n_steps, const float* qp_in, const float* obs_in,
+                          const float* done_in, const float* steps_in, const uint32_t* rng_in,
+                          const bx_policy* policy, uint64_t seed, uint64_t offset,
+                          uint64_t step_stride, float* act_out, float* raw_out, float* logp_out,
+                          float* out, uint32_t* rng_out, void* stream);
+
 /* Batched System.default_qp from per-env joint angles/velocities
  * (B, num_joint_dof) contiguous (system.py:112-242). */
 int bx_system_default_qp(bx_system* sys, int64_t n_envs,
@@ -500,6 +558,13 @@ int bx_uniform_epoch(float* out, int64_t n, uint64_t seed, uint64_t offset,
 int bx_uniform_slabs(float* out, int64_t slab_n, int64_t n_slabs, uint64_t seed,
                      uint64_t offset, uint64_t slab_stride, const int64_t* epoch,
                      uint64_t epoch_stride, float lo, float hi, void* stream);
+
+/* Standard normals over the same slabs: out[s * slab_n + j] = N(seed, offset +
+ * (*epoch) * epoch_stride + s * slab_stride + 2 j), N as bx_env_rollout_policy
+ * defines it (each sample takes two counters; ABI 14). */
+int bx_normal_slabs(float* out, int64_t slab_n, int64_t n_slabs, uint64_t seed,
+                    uint64_t offset, uint64_t slab_stride, const int64_t* epoch,
+                    uint64_t epoch_stride, void* stream);
 
 /*
  * Standalone HBM-streaming phase kernels over a structure-of-arrays batch
