@@ -159,11 +159,15 @@ class AutoResetWrapper(Wrapper):
   def _select(state):
     done = state.done != 0
     fq, fo = state.info['first_qp'], state.info['first_obs']
-    d3 = done.reshape(-1, 1, 1)
     from brax_amd.base import QP  # pylint: disable=import-outside-toplevel
-    qp = QP(pos=torch.where(d3, fq.pos, state.qp.pos), rot=torch.where(d3, fq.rot, state.qp.rot),
-            vel=torch.where(d3, fq.vel, state.qp.vel), ang=torch.where(d3, fq.ang, state.qp.ang))
-    obs = torch.where(done.reshape(-1, 1), fo, state.obs)
+
+    def sel(first, now):
+      # done (B,) against a field of any rank (B, ...): Fast's qp has no body
+      # axis, where a fixed (B, 1, 1) mask would broadcast to (B, B, 1)
+      return torch.where(done.reshape((-1,) + (1,) * (now.dim() - 1)), first, now)
+    qp = QP(pos=sel(fq.pos, state.qp.pos), rot=sel(fq.rot, state.qp.rot),
+            vel=sel(fq.vel, state.qp.vel), ang=sel(fq.ang, state.qp.ang))
+    obs = sel(fo, state.obs)
     return state.replace(qp=qp, obs=obs)
 
 

@@ -247,3 +247,61 @@ def normwise(a, b):
 
 
 QP_FIELDS = {'pos': slice(0, 3), 'rot': slice(3, 7), 'vel': slice(7, 10), 'ang': slice(10, 13)}
+
+
+# ---------------------------------------------------------------------------
+# the counter RNG restated on the host (include/brax_amd.h): plain
+# numpy from the formulas, no call into the library
+# ---------------------------------------------------------------------------
+_U64 = (1 << 64) - 1
+
+
+def _u64(x):
+  """Python ints (any sign or size) or arrays as wrapping uint64."""
+  if isinstance(x, (int, np.integer)):
+    return np.uint64(int(x) & _U64)
+  x = np.asarray(x)
+  if x.dtype == np.uint64:
+    return x
+  if x.dtype == object:
+    return np.array([int(v) & _U64 for v in x.ravel()], np.uint64).reshape(x.shape)
+  return x.astype(np.uint64)
+
+
+def counters(offset, n, step=1):
+  """The n counters offset + step * j, j = 0..n-1, wrapping in uint64."""
+  with np.errstate(over='ignore'):
+    return _u64(offset) + _u64(step) * np.arange(n, dtype=np.uint64)
+
+
+def splitmix_bits(seed, idx):
+  """The 24 bits behind a draw: splitmix64 of seed * 0x9E3779B97F4A7C15 + idx +
+  0x632BE59BD9B4E019 in wrapping uint64, its top 24 bits (z >> 40)."""
+  with np.errstate(over='ignore'):
+    z = _u64(seed) * np.uint64(0x9E3779B97F4A7C15) + _u64(idx) + np.uint64(0x632BE59BD9B4E019)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    z = z ^ (z >> np.uint64(31))
+  return z >> np.uint64(40)
+
+
+def uniform01_ref(seed, idx):
+  """U(seed, idx) in [0, 1) as float64: (z >> 40) / 2^24, a 24-bit value, so
+  its float32 cast is exact."""
+  return splitmix_bits(seed, idx).astype(np.float64) / 16777216.0
+
+
+def normal_ref(seed, idx, dtype=np.float64):
+  """N(seed, idx): Box-Muller's cosine branch on counters idx and idx + 1,
+  sqrt(-2 ln(1 - U_idx)) cos(2 pi U_{idx+1}), every operation in `dtype`."""
+  dt = np.dtype(dtype).type
+  idx = _u64(idx)
+  with np.errstate(over='ignore'):
+    nxt = idx + np.uint64(1)
+  u0 = uniform01_ref(seed, idx).astype(dt)
+  u1 = uniform01_ref(seed, nxt).astype(dt)
+  r = np.sqrt(dt(-2.0) * np.log(dt(1.0) - u0))
+  c = np.cos(dt(2.0 * np.pi) * u1)
+  out = r * c
+  assert out.dtype == np.dtype(dtype)
+  return out

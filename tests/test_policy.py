@@ -129,6 +129,34 @@ def test_forward_scale_floor_and_tanh_log_det():
     assert float(lg[0, 0]) == pytest.approx(fn(1.5) + 2.0 * fn(-0.75), rel=1e-14)
 
 
+def test_chained_rollout_on_the_torch_only_env():
+  """Fast has no kernel form and a qp without a body axis: the chained path
+  under Episode + AutoReset keeps every step's shapes (the AutoReset select
+  masks each field at its own rank), and a finished episode restarts from the
+  first state, each env for itself."""
+  from brax_amd.envs import wrappers
+  from brax_amd.envs.fast import Fast
+  from brax_amd.envs.policy import fused_supported, policy_rollout
+  B, K = 3, 5
+  env = wrappers.AutoResetWrapper(wrappers.EpisodeWrapper(Fast(batch_size=B, device='cpu'), 2, 1))
+  st0 = env.reset(np.array([1, 2], np.uint32))
+  assert tuple(st0.obs.shape) == (B, 2)
+  p = MLPPolicy([([[0.0, 0.0], [0.0, 0.0]], [1.0, 0.0])], deterministic=True)  # action tanh(1) > 0
+  assert fused_supported(env, p)
+  with pytest.raises(NotImplementedError):
+    policy_rollout(env, st0, p, K, fused=True)
+  final, tr, ex = policy_rollout(env, st0, p, K)
+  assert tuple(tr.obs.shape) == (K, B, 2) and tuple(tr.qp.shape) == (K, B, 16)
+  assert tuple(ex.action.shape) == (K, B, 1) and tuple(ex.log_prob.shape) == (K, B)
+  assert tr.done.tolist() == [[0.0] * B, [1.0] * B, [0.0] * B, [1.0] * B, [0.0] * B]
+  # vel += dt, pos += vel dt (dt 0.02) from the restored zero state
+  dt = 0.02
+  one, two = [dt * dt, dt], [0.0, 0.0]
+  want = torch.tensor([[one] * B, [two] * B, [one] * B, [two] * B, [one] * B], dtype=torch.float32)
+  assert torch.allclose(tr.obs, want, rtol=1e-6, atol=0.0)
+  assert torch.equal(final.obs, tr.obs[-1])
+
+
 def test_abi_version_and_header():
   assert abi.ABI_VERSION == 14
   src = open(os.path.join(ROOT, 'include', 'brax_amd.h')).read()
