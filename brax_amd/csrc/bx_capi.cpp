@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/brax_amd.h"
+#include "pbd_features.h"
 #include "pbd_launch.h"
 #include "pbd_layout.h"
 
@@ -74,6 +75,7 @@ struct bx_system {
   int64_t movf_envs = 0;
   int fold = 0;     // every joint j has torque actuator j (the Ant / Humanoid env kernels)
   int jb = 0;       // the joint-halves env kernels may own body copies (JB, build_blob)
+  int cb = 0;       // and may resolve each body's contact row on its lanes (CB, build_blob)
   size_t lds_env = 0;    // bytes per block for the per-env kernels
   size_t lds_reset = 0;  // bytes per block for default_qp
 };
@@ -673,6 +675,22 @@ int build_blob(const bx_desc* d, const bx_reset_desc* r, bx_system* S) {
     }
     return true;
   };
+  // CB's row conditions (the JB kernels that resolve a body's contact row on
+  // the body's own lanes, pbd_features.h cb_feat): one collider group of
+  // one-way capsule-plane rows, each against a body on no joint side (frozen
+  // under jb_bodies_ok), at most one row per a body. row_of: that row, or -1
+  std::vector<int> row_of(N, -1);
+  auto cb_rows_ok = [&]() {
+    if (G != 1 || d->col_fn[0] != BX_COL_CAPSULE_PLANE || !d->col_oneway[0]) return false;
+    std::vector<char> side(N, 0);
+    for (int j = 0; j < J; j++) side[d->joint_body_p[j]] = side[d->joint_body_c[j]] = 1;
+    std::vector<int> rows(N, 0);
+    for (int x = 0; x < R; x++) {
+      if (side[d->row_body_b[x]] || ++rows[d->row_body_a[x]] > 1) return false;
+    }
+    return true;
+  };
+  for (int x = R - 1; x >= 0; x--) row_of[d->row_body_a[x]] = x;
   const int HB = 8;  // the joint halves' half width (lanes per side)
   // a contact row's 32 resolved words (LR_*): its record's geometry and
   // constants with the masses / inverse inertias of the bodies it names
@@ -932,6 +950,14 @@ int build_blob(const bx_desc* d, const bx_reset_desc* r, bx_system* S) {
         uint32_t czj = (uint32_t)(2 * R);
         if (hasS && !cl[body].empty()) czj |= (uint32_t)cl[body][0] & 0x7F000000u;
         put_list(l, LI_CL_J, cl[body], hasS, czj);
+        // CB: the side body's row (row 0's record where it has none)
+        if (R > 0) {
+          const int x = hasS ? row_of[body] : -1;
+          uint32_t rw[32];
+          row_words(x >= 0 ? x : 0, rw);
+          for (int k = 0; k < 32; k++) put(l, LI_ROW_J + k, rw[k]);
+          put(l, LI_ROW_J + LRJ_HAS, x >= 0 ? 1u : 0u);
+        }
       }
       put_act(l, LI_ACT_H, jh < K ? jh : 0);
       if (R > 0) {
@@ -993,6 +1019,12 @@ int build_blob(const bx_desc* d, const bx_reset_desc* r, bx_system* S) {
     const bool jb_off = getenv("BX_NO_JB") && atoi(getenv("BX_NO_JB"));
     const bool jb = S->fold && (f & 128) && !(f & 16) && L == 16 && !jb_off && jb_bodies_ok();
     S->jb = jb ? 1 : 0;
+    // CB: a JB system whose rows its kernel can resolve on the body lanes
+    // (cb_rows_ok). The Ant kind's own kernels are compiled that way
+    // (cb_feat), so an Ant-kind system without it takes the all-kinds kernel
+    S->cb = (jb && cb_feat(f) && cb_rows_ok()) ? 1 : 0;
+    if (getenv("BX_PLAN_DEBUG"))
+      fprintf(stderr, "bx plan: fold=%d body_copies=%d contact_on_body=%d\n", S->fold, S->jb, S->cb);
   }
   // the MULTI kernel is instantiated for the lean feature set (revolute,
   // torque, capsule-plane / capsule-capsule, no forces)
@@ -1367,10 +1399,10 @@ static int env_step_impl(bx_system* S, const bx_env_params* env, int64_t n_envs,
   }
   if (pol)  // (policy_plan admits SINGLE-mode systems only)
     HIP_OK(launch_env_policy_single(S->L, S->feat, S->gw, S->tpb, n_envs, pol_lds, as_stream(stream), a,
-                                    *pol, S->fold ? (1 | (S->jb ? 2 : 0)) : 0));
+                                    *pol, S->fold ? (1 | (S->jb ? 2 : 0) | (S->cb ? 4 : 0)) : 0));
   else if (S->mode == 1)
     HIP_OK(launch_env_step_single(S->L, S->feat, S->gw, S->tpb, n_envs, step_lds(S), as_stream(stream), a,
-                                  S->fold ? (1 | (S->jb ? 2 : 0)) : 0));
+                                  S->fold ? (1 | (S->jb ? 2 : 0) | (S->cb ? 4 : 0)) : 0));
   else if (S->mode == 3)  // MULTI-mode systems step envs with the item-loop kernel
     HIP_OK(launch_env_step_generic(S->L, 0, S->feat, S->tpb, n_envs,
                                    (size_t)S->hdr.env_words * 4, as_stream(stream), a));

@@ -44,6 +44,21 @@ enum { F_CCO = 2048 };
 // Ant Mountain, the culled scenes)
 enum { F_LEAN = F_CC | F_TW };
 
+// CB (contact on body lanes): the feature sets whose body-copy kernels (JB,
+// pbd_step_single) resolve each body's one contact row on the body's own
+// lanes: joint halves, one collider group, one-way capsule-plane rows only,
+// one row slot and no forces (the Ant env kernels). The host admits a system
+// to such a kernel only when its rows fit (bx_capi.cpp cb_rows_ok).
+// A/B switch -DBX_NO_CB: the same kernels with the row-lane passes.
+constexpr bool cb_feat(int F) {
+#if defined(BX_NO_CB)
+  return false;
+#else
+  return (F & F_JH) != 0 && (F & F_G1) != 0 &&
+         (F & (F_CC | F_TW | F_R2 | F_C16 | F_FORCE | F_SPH)) == 0;
+#endif
+}
+
 #if defined(__HIPCC__)
 template <int F, int M> __device__ __forceinline__ constexpr int cl_width() {
   return (F & F_C16) ? 16 : M;

@@ -2510,11 +2510,13 @@ struct Hoist {
 // JH (joint halves): lanes j and j + 8 of an env's 16 both hold joint j and
 // actuator j. JB (JH, the Ant / HalfCheetah env kernels): the lane's body is
 // its side's (parent of joint j on lane j, child on lane j + 8), a copy per
-// side lane
-template <int M, bool JH, bool R2 = false, int MC = M, bool JB = false>
+// side lane. CB (JB, pbd_features.h cb_feat): the lane's row is its side
+// body's (LI_ROW_J, hasR: the body has one), and no contact list is loaded
+template <int M, bool JH, bool R2 = false, int MC = M, bool JB = false, bool CB = false>
 __device__ __forceinline__ void load_hoist(const uint32_t* img, const BlobHdr& H, int lane,
                                            Hoist<M, MC>& X) {
   static_assert(!JB || (JH && MC <= 8), "JB: joint halves, <= 8 contact entries");
+  static_assert(!CB || (JB && !R2), "CB: body copies, one row slot");
   const int jx = JH ? (lane & 7) : lane;
   X.hasB = JB ? jx < H.J : lane < H.N;
   X.hasJ = jx < H.J;
@@ -2540,14 +2542,15 @@ __device__ __forceinline__ void load_hoist(const uint32_t* img, const BlobHdr& H
   grab(OB, 16);
   grab(OJ, 48);
   grab(OA, 8);
-  grab(LI_ROW, 32);
+  constexpr int OR = CB ? LI_ROW_J : LI_ROW;
+  grab(OR, CB ? 36 : 32);
   if constexpr (R2) {
     grab(LI_ROW2, 32);
     grab(LI_RIDX, 4);
   }
   grab(OJL, M);
   grab(OAL, M);
-  grab(OCL, MC < 8 ? MC : 8);
+  if constexpr (!CB) grab(OCL, MC < 8 ? MC : 8);
   if constexpr (MC > 8) grab(LI_CL2, 8);
   constexpr int OL = JH ? LI_JLIM_H : LI_JLIM;
   grab(OL, 8);
@@ -2611,7 +2614,8 @@ __device__ __forceinline__ void load_hoist(const uint32_t* img, const BlobHdr& H
     R.Ia = f3(o + LR_IA);
     R.Ib = f3(o + LR_IB);
   };
-  row(LI_ROW, X.R);
+  row(OR, X.R);
+  if constexpr (CB) X.hasR = X.hasB && n(OR + LRJ_HAS) != 0;
   if constexpr (R2) {
     row(LI_ROW2, X.R2);
     X.r1 = n(LI_RIDX);
@@ -2636,8 +2640,10 @@ __device__ __forceinline__ void load_hoist(const uint32_t* img, const BlobHdr& H
     X.jl.e[k] = n(OJL + k);
     X.al.e[k] = n(OAL + k);
   }
+  if constexpr (!CB) {
 #pragma unroll
-  for (int k = 0; k < MC; k++) X.cl.e[k] = n(k < 8 ? OCL + k : LI_CL2 + k - 8);
+    for (int k = 0; k < MC; k++) X.cl.e[k] = n(k < 8 ? OCL + k : LI_CL2 + k - 8);
+  }
 }
 
 // the spherical SINGLE kernels' limit rows into LDS, once per launch (see
@@ -2718,6 +2724,18 @@ __device__ __forceinline__ void gsum_contact(const GList<M>& g, const float* csl
          r0.z / d0 + r1.z / d1};
 }
 
+// gsum_contact's one-group sums of a body whose only entry is the slot (v, q,
+// count f), from registers (CB): the sum from zero, the padding entries'
+// exact zeros left out (x + 0 = x)
+__device__ __forceinline__ void own_contact(v3 v, q4 q, float f, float eps, v3& a, q4& r) {
+  BX_IEEE_IN_CONTACT
+  const v3 a0 = mk(0.f, 0.f, 0.f) + v;
+  const q4 r0 = q4{0.f, 0.f, 0.f, 0.f} + q;
+  const float d0 = eps + (0.f + f);
+  a = a0 / d0;
+  r = q4{r0.w / d0, r0.x / d0, r0.y / d0, r0.z / d0};
+}
+
 // Euler.velocity_projection (integrators.py:122-146) on one body
 __device__ __forceinline__ void vproj(QP& q, v3 ppos, q4 prot, const BodyC& B, float h,
                                       bool bare = false, bool fast = false) {
@@ -2789,6 +2807,13 @@ __device__ void pbd_step_single(const Cst& c, const BlobHdr& H, const Env& E, in
   // loaded record
   // (no body copies with 16-entry contact lists: Pusher folds only)
   constexpr bool JB = FOLD && JH && (F & F_C16) == 0;
+  // CB (JB kernels of one-way capsule-plane rows, one per body, against
+  // frozen bodies: pbd_features.h cb_feat, checked on the host): the lane
+  // resolves its body's row itself, from the copy in its registers, so the
+  // contact passes exchange nothing through LDS (no row slots, no gathers, no
+  // records written for another lane to read); the arithmetic is the row
+  // lane's and the gather's, operand for operand
+  constexpr bool CB = JB && cb_feat(F);
   const int bi = JB ? X.S.body : lane;  // the lane's body
   float* myqp = E.qp + bi * QP_STRIDE;
   QP q;
@@ -2838,7 +2863,8 @@ __device__ void pbd_step_single(const Cst& c, const BlobHdr& H, const Env& E, in
     for (int sub = 0; sub < 2; sub++) {
       ppos = q.pos;
       prot = q.rot;
-      if (sub == 1 && hasB) st_slot(E.prev + bi * PREV_STRIDE, ppos, prot, 0.f);
+      // (CB: the position pass takes ppos / prot themselves)
+      if (!CB && sub == 1 && hasB) st_slot(E.prev + bi * PREV_STRIDE, ppos, prot, 0.f);
       // actuators + damping (actuator a drives joint a when H.act_same)
       if constexpr (JH) {
         // one side of joint / actuator jx per lane (act_same, checked on the host)
@@ -2940,8 +2966,9 @@ __device__ void pbd_step_single(const Cst& c, const BlobHdr& H, const Env& E, in
         q.rot = q4{q.rot.w + dr.w * X.B.qm.w, q.rot.x + dr.x * X.B.qm.x, q.rot.y + dr.y * X.B.qm.y,
                    q.rot.z + dr.z * X.B.qm.z};
         if (sub == 0) vproj(q, ppos, prot, X.B, h, JB);
-        // JB: the record is read next by the contact passes (after sub 1)
-        if (!JB || sub == 1) stqp(myqp, q);
+        // JB: the record is read next by the contact passes (after sub 1;
+        // CB: by nothing before the velocity pass's update writes it)
+        if (!JB || (!CB && sub == 1)) stqp(myqp, q);
       }
       phase_sync();
       BX_STAMP(3);
@@ -2967,6 +2994,80 @@ __device__ void pbd_step_single(const Cst& c, const BlobHdr& H, const Env& E, in
     // substep) keep the straight-line code
     const v3 z3 = mk(0.f, 0.f, 0.f);
     const q4 z4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (CB) {
+      // The four stretches of the passes below, each on the body's lane: the
+      // row's a body is the lane's q, its previous-substep pose ppos / prot,
+      // its slot and row data stay in registers; the b body is frozen (its
+      // records: the prologue's). A lane whose body has no row runs the same
+      // instructions on row 0's constants and takes the zero slot's sums.
+      // `held` stands where a value went through LDS, so each stretch
+      // contracts its products as it did between its loads and stores
+      const RowC& R = X.R;
+      v3 oap = z3, oav = z3, oaa = z3, rop = z3, rov = z3, roa = z3;
+      q4 oar = z4;
+      if (hasB) {
+        const QP b = ldqp(E.qp + R.b * QP_STRIDE);
+        v3 pbp, obp, cvel;
+        q4 pbr, obr;
+        float unused;
+        ld_slot(E.prev + R.b * PREV_STRIDE, pbp, pbr, unused);
+        contact_gen<F>(R, q, b, cpos, cvel, cn, pen);
+        dl = position_contact<F>(R, q, b, ppos, prot, pbp, pbr, cpos, cn, pen, oap, oar, obp, obr);
+        if (!X.hasR) {
+          oap = z3;
+          oar = z4;
+        }
+        held(oap);
+        held(oar);
+      }
+      BX_STAMP(4);
+      if (hasB) {
+        v3 dp;
+        q4 dr;
+        own_contact(oap, oar, nonzero3(oap), 1e-6f, dp, dr);
+        q.pos = q.pos + mul(dp, X.B.pm);
+        q.rot = q4{q.rot.w + dr.w * X.B.qm.w, q.rot.x + dr.x * X.B.qm.x, q.rot.y + dr.y * X.B.qm.y,
+                   q.rot.z + dr.z * X.B.qm.z};
+        // qp_right_before of the velocity pass (the rb record)
+        rop = q.pos;
+        rov = q.vel;
+        roa = q.ang;
+        vproj(q, ppos, prot, X.B, h, JB);
+        held(q.pos); held(q.rot); held(q.vel); held(q.ang);
+        held(rop); held(rov); held(roa);
+        held(cpos); held(cn); held(pen); held(dl);
+      }
+      BX_STAMP(5);
+      if (hasB) {
+        const QP b = ldqp(E.qp + R.b * QP_STRIDE);
+        v3 rbp, rbv, rba, obv, oba;
+        ld_rb(E.rb + R.b * RB_STRIDE, rbp, rbv, rba);
+        velocity_contact<F>(R, h, q, b, rop, rov, roa, rbp, rbv, rba, cpos, cn, pen, dl, oav, oaa,
+                            obv, oba);
+        if (!X.hasR) {
+          oav = z3;
+          oaa = z3;
+        }
+        held(oav);
+        held(oaa);
+      }
+      BX_STAMP(6);
+      if (hasB) {
+        v3 dv;
+        q4 da;
+        own_contact(oav, q4{0.f, oaa.x, oaa.y, oaa.z}, nonzero3(oav), 1e-6f, dv, da);
+        v3 dav = mk(da.x, da.y, da.z);
+        q.vel = mul(q.vel + dv, X.B.pm);
+        q.ang = mul(q.ang + dav, X.B.rm);
+        stqp(myqp, q);
+        icv = icv + dv;
+        ica = ica + dav;
+        iaa = iaa + dpa_last;
+      }
+      phase_sync();
+      BX_STAMP(7);
+      continue;
+    }
     auto pos_pass = [&](auto fc, const RowC& R, int r, v3& cpos, v3& cn, float& pen, float& dl) {
       constexpr int FS = decltype(fc)::value;
       QP a = ldqp(E.qp + R.a * QP_STRIDE), b = ldqp(E.qp + R.b * QP_STRIDE);
@@ -3120,7 +3221,7 @@ __device__ void pbd_step_single(const Cst& c, const BlobHdr& H, const Env& E, in
     // slots carried zeros). A body's state is NaN at the end of the step
     // exactly when a contact pass of the step saw it NaN (a one-way row's
     // contact is its body's; the two-way passes carry NaN rows explicitly)
-    if ((X.cl.e[0] & 0xFFFFFF) != 2 * H.R) {
+    if (CB ? X.hasR : (X.cl.e[0] & 0xFFFFFF) != 2 * H.R) {
       const float pz = nan_of(((q.pos.x + q.pos.y) + (q.pos.z + q.rot.w)) +
                               ((q.rot.x + q.rot.y) + (q.rot.z + q.vel.x)) +
                               ((q.vel.y + q.vel.z) + (q.ang.x + q.ang.y)) + q.ang.z);
@@ -4684,9 +4785,11 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   // kernels keep the order their main loop was tuned with)
   Hoist<M, cl_width<F, M>()> X;
   // JB: the env-program kernels with joint halves (pbd_step_single's FOLD && JH)
+  // (the lane's hoisted body is then its joint side's, not body lane)
+  constexpr bool JBK = S && (F & F_JH) != 0 && EK != EK_ANY && (F & F_C16) == 0;
   if constexpr (S && ONE)
-    load_hoist<M, (F & F_JH) != 0, (F & F_R2) != 0, cl_width<F, M>(),
-               (F & F_JH) != 0 && EK != EK_ANY && (F & F_C16) == 0>(A.lane_img, H, lane, X);
+    load_hoist<M, (F & F_JH) != 0, (F & F_R2) != 0, cl_width<F, M>(), JBK, JBK && cb_feat(F)>(
+        A.lane_img, H, lane, X);
   Env E = carve(ebase + le * H.env_words, H);
   zero_slots(E, H, lane);
   BX_PSTAMP(5);
@@ -4695,12 +4798,12 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   const int aw = (int)A.act_width;
   const int64_t el = valid ? e : 0;
   if constexpr (S && !ONE)
-    load_hoist<M, (F & F_JH) != 0, (F & F_R2) != 0, cl_width<F, M>(),
-               (F & F_JH) != 0 && EK != EK_ANY && (F & F_C16) == 0>(A.blob + H.o_lane, H, lane, X);
+    load_hoist<M, (F & F_JH) != 0, (F & F_R2) != 0, cl_width<F, M>(), JBK, JBK && cb_feat(F)>(
+        A.blob + H.o_lane, H, lane, X);
   if constexpr (S) stage_lim<L, F>(ONE ? A.lane_img : A.blob + H.o_lane, H, E, lane);
   // the bodies' masses for humanoid_com (its lmass): lane b's hoisted body b
   // (the SINGLE kernels without body copies), into E.red + 16 once per launch
-  if constexpr (S && L == 16 && !((F & F_JH) != 0 && EK != EK_ANY && (F & F_C16) == 0))
+  if constexpr (S && L == 16 && !JBK)
     E.red[16 + lane] = X.B.mass;
   BX_PSTAMP(6);
   // AutoResetWrapper.step: steps zeroed where the incoming done is set; done := 0
@@ -4965,8 +5068,6 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
     // the Humanoid kernel's actuators drive the joints of their own index
     // (its launch requires fold), so its observation takes the lane's
     // hoisted body, joint and actuator
-    // (JB: the lane's hoisted body is its joint side's, not body lane)
-    constexpr bool JBK = S && (F & F_JH) != 0 && EK != EK_ANY && (F & F_C16) == 0;
     env_observe<L, EK>(c, H, E, lane, kind, P.obs_flags, P.obs_size, act, aw,
                    valid ? (POL ? pobs : O.obs + e * P.obs_size) : nullptr, P.coef, S ? &X.J : nullptr,
                    (S && !JBK) ? &X.B : nullptr, (S && EK == EK_HUM) ? &X.A : nullptr);

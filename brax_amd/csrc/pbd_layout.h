@@ -147,8 +147,14 @@ enum {
   LI_JL_J = 292,
   LI_AL_J = 300,
   LI_CL_J = 308,
-  LANE_W = 316
+  // CB (the JB kernels that resolve a body's contact row on its own lanes,
+  // pbd_features.h cb_feat): the row (LR_*) whose a body is the lane's SIDE
+  // body, then LRJ_HAS (1: that body has a row; 0: none, the record is row
+  // 0's). Loaded in place of LI_ROW and LI_CL_J
+  LI_ROW_J = 316,
+  LANE_W = 352
 };
+enum { LRJ_HAS = 32 };  // (past the LR_* words; the region is 36 words)
 // MULTI-mode joint halves: lane l works side (l & 8: child) of joint
 // (l >> 4) * 8 + (l & 7) and that joint's actuator, the Ant kernel's halves
 // in every 16-lane row of the env's 256; word w of lane l at o_mjh +

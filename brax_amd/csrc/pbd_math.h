@@ -221,6 +221,12 @@ __device__ __forceinline__ bool is_nan(float x) {
   asm("" : "+v"(x));
   return (__float_as_uint(x) & 0x7fffffffu) > 0x7f800000u;
 }
+// an opaque copy in place (no instruction): what the compiler knows of how x
+// was computed ends here, as it does where a value goes through LDS, so it
+// fuses no product into a later sum across this point
+__device__ __forceinline__ void held(float& x) { asm("" : "+v"(x)); }
+__device__ __forceinline__ void held(v3& a) { held(a.x); held(a.y); held(a.z); }
+__device__ __forceinline__ void held(q4& a) { held(a.w); held(a.x); held(a.y); held(a.z); }
 // 0, or a quiet NaN when x is NaN (itself opaque, so no NaN-free assumption
 // removes it). The reference multiplies its contact impulses by 0 / 1 masks
 // (`p = dlambda * n * coll_mask`, colliders.py:332-333; `* apply_n`,

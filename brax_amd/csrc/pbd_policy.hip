@@ -55,7 +55,8 @@ hipError_t launch_env_policy_single(int L, int feat, int gw, int tpb, int64_t n_
   dim3 grid((unsigned)((n_envs + epb - 1) / epb));
   const int k = a.P.kind;
   const bool jb = (fold & 2) != 0;
-  if (fold && jb && L == 16 && gw <= 4 && k == BX_ENV_ANT && feat == (F_G1 | F_JH)) {
+  const bool ant_ok = jb && ((fold & 4) != 0 || !cb_feat(F_G1 | F_JH));
+  if (fold && ant_ok && L == 16 && gw <= 4 && k == BX_ENV_ANT && feat == (F_G1 | F_JH)) {
     const bool wide = (int64_t)grid.x * (tpb / 64 > 0 ? tpb / 64 : 1) > 4 * (int64_t)cu_count();
     if (wide)
       launch_pol(env_policy_rollout_wide_kernel<16, 1, F_G1 | F_JH, 4, EK_ANT>, grid, tpb, lds, s, a, q);

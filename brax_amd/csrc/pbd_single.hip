@@ -99,7 +99,11 @@ hipError_t launch_env_step_single(int L, int feat, int gw, int tpb, int64_t n_en
   // bit 0 = every joint j has torque actuator j; the joint-halves kernels
   // also give each side lane its body's copy: bit 1 = the system allows it)
   const bool jb = (fold & 2) != 0;
-  if (fold && jb && L == 16 && gw <= 4 && k == BX_ENV_ANT && feat == (F_G1 | F_JH)) {
+  // (the Ant kernels resolve contacts on the body lanes, cb_feat: bit 2 = the
+  // system's rows allow it; an Ant-kind system without it takes the variant
+  // list's all-kinds kernel below)
+  const bool ant_ok = jb && ((fold & 4) != 0 || !cb_feat(F_G1 | F_JH));
+  if (fold && ant_ok && L == 16 && gw <= 4 && k == BX_ENV_ANT && feat == (F_G1 | F_JH)) {
     // past one wave per SIMD: the register-capped kernels
     const bool wide = (int64_t)grid.x * (tpb / 64 > 0 ? tpb / 64 : 1) > 4 * (int64_t)cu_count();
     // (a packed single step at a wide batch takes the wide rollout kernel)
