@@ -89,6 +89,8 @@ _SIGS = {
                                C.POINTER(abi.BxPolicy), C.c_uint64, C.c_uint64, C.c_uint64,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p], C.c_int),
+    'bx_env_eval_policy': abi.SIGNATURES['bx_env_eval_policy'],
+    'bx_env_eval_packed': abi.SIGNATURES['bx_env_eval_packed'],
 }
 
 EXPORTS = tuple(_SIGS)

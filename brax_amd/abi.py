@@ -109,6 +109,26 @@ class BxPolicy(C.Structure):
               ('deterministic', C.c_int32), ('action_size', C.c_int32)]
 
 
+# The evaluation entry points, argument by argument in the header's order
+# (name, ctypes type); `eval_in` / `eval_out` are (M + 3, B) float32: the M
+# metric sums in the env's metric order, the reward sum, active_episodes,
+# episode_steps.
+_vp = C.c_void_p
+EVAL_POLICY_ARGS = (
+    ('sys', _vp), ('env', C.POINTER(BxEnvParams)), ('n_envs', C.c_int64), ('n_steps', C.c_int32),
+    ('qp_in', _vp), ('obs_in', _vp), ('done_in', _vp), ('steps_in', _vp), ('rng_in', _vp),
+    ('policy', C.POINTER(BxPolicy)), ('seed', C.c_uint64), ('offset', C.c_uint64),
+    ('step_stride', C.c_uint64), ('eval_in', _vp), ('out', _vp), ('eval_out', _vp),
+    ('rng_out', _vp), ('stream', _vp))
+EVAL_PACKED_ARGS = (
+    ('sys', _vp), ('env', C.POINTER(BxEnvParams)), ('n_envs', C.c_int64), ('n_steps', C.c_int32),
+    ('qp_in', _vp), ('done_in', _vp), ('steps_in', _vp), ('rng_in', _vp), ('act', _vp),
+    ('act_stride', C.c_int64), ('act_step_stride', C.c_int64), ('act_width', C.c_int64),
+    ('eval_in', _vp), ('out', _vp), ('eval_out', _vp), ('rng_out', _vp), ('stream', _vp))
+ARGS = {'bx_env_eval_policy': EVAL_POLICY_ARGS, 'bx_env_eval_packed': EVAL_PACKED_ARGS}
+SIGNATURES = {name: ([t for _, t in args], C.c_int) for name, args in ARGS.items()}
+
+
 def _arr(x, dtype):
   a = np.ascontiguousarray(np.asarray(x, dtype=dtype))
   if a.size == 0:

@@ -1353,7 +1353,8 @@ static int env_step_impl(bx_system* S, const bx_env_params* env, int64_t n_envs,
                          int64_t act_width, const bx_env_state* out, void* stream,
                          int32_t n_steps, int64_t act_step, int64_t out_step, int64_t rng_step,
                          const DrawSpec* draw = nullptr, bool packed = false,
-                         const PolArgs* pol = nullptr, size_t pol_lds = 0) {
+                         const PolArgs* pol = nullptr, size_t pol_lds = 0,
+                         const EvalArgs* evl = nullptr, size_t evl_lds = 0) {
   if (!S || !env || !in || !out) return fail("null argument");
   DEVICE_SCOPE(S);
   if (check_env(S, env)) return 1;
@@ -1397,7 +1398,14 @@ static int env_step_impl(bx_system* S, const bx_env_params* env, int64_t n_envs,
     a.draw_hi = draw->hi;
     a.act_out = draw->act_out;
   }
-  if (pol)  // (policy_plan admits SINGLE-mode systems only)
+  const int fold = S->fold ? (1 | (S->jb ? 2 : 0) | (S->cb ? 4 : 0)) : 0;
+  if (evl && pol)  // (eval_plan admits SINGLE-mode systems only)
+    HIP_OK(launch_env_eval_policy(S->L, S->feat, S->gw, S->tpb, n_envs, evl_lds, as_stream(stream), a, *pol,
+                                  *evl, fold));
+  else if (evl)
+    HIP_OK(launch_env_eval_open(S->L, S->feat, S->gw, S->tpb, n_envs, evl_lds, as_stream(stream), a, *evl,
+                                fold));
+  else if (pol)  // (policy_plan admits SINGLE-mode systems only)
     HIP_OK(launch_env_policy_single(S->L, S->feat, S->gw, S->tpb, n_envs, pol_lds, as_stream(stream), a,
                                     *pol, S->fold ? (1 | (S->jb ? 2 : 0) | (S->cb ? 4 : 0)) : 0));
   else if (S->mode == 1)
@@ -1422,7 +1430,8 @@ static int env_step_packed(bx_system* S, const bx_env_params* env, int64_t n_env
                            const uint32_t* rng_in, const float* act, int64_t act_stride,
                            int64_t act_step, int64_t act_width, float* out, uint32_t* rng_out,
                            void* stream, const DrawSpec* draw = nullptr,
-                           const PolArgs* pol = nullptr, size_t pol_lds = 0) {
+                           const PolArgs* pol = nullptr, size_t pol_lds = 0,
+                           const EvalArgs* evl = nullptr, size_t evl_lds = 0) {
   if (!S || !env) return fail("null argument");
   if (n_envs <= 0) {
     if (check_env(S, env)) return 1;
@@ -1458,7 +1467,7 @@ static int env_step_packed(bx_system* S, const bx_env_params* env, int64_t n_env
   // one step's output block: qp | obs | reward, done, steps, truncation | metrics
   const int64_t block = B * (N * 16 + env->obs_size + 4 + env->n_metrics);
   return env_step_impl(S, env, n_envs, &in, act, act_stride, act_width, &o, stream, n_steps,
-                       act_step, block, B, draw, true, pol, pol_lds);
+                       act_step, block, B, draw, true, pol, pol_lds, evl, evl_lds);
 }
 
 int bx_env_step_packed(bx_system* S, const bx_env_params* env, int64_t n_envs,
@@ -1572,6 +1581,69 @@ int bx_env_rollout_policy(bx_system* S, const bx_env_params* env, int64_t n_envs
   const DrawSpec d{0, 0, 0, 0.f, 0.f, act_out};
   return env_step_packed(S, env, n_envs, n_steps, qp_in, done_in, steps_in, rng_in, nullptr, 0, 0,
                          A, out, rng_out, stream, &d, &q, lds);
+}
+
+// the evaluation kernels' on-chip words laid out past `base` bytes of the
+// workgroup's LDS (the system's areas, or the policy's): per env the M + 3
+// evaluation words and the step's M metrics
+static int eval_plan(const bx_system* S, const bx_env_params* env, size_t base, EvalArgs* V,
+                     size_t* lds) {
+  if (S->mode != 1) return fail("the evaluation kernels need a SINGLE-mode system");
+  base = (base + 15) & ~(size_t)15;
+  V->lds_off = (int32_t)(base / 4);
+  V->words = (2 * env->n_metrics + 3 + 3) & ~3;
+  *lds = base + (size_t)(S->tpb / S->L) * V->words * 4;
+  if (*lds > 160 * 1024) return fail("evaluation: the workgroup's LDS exceeds 160 KiB");
+  return 0;
+}
+
+int bx_env_eval_policy(bx_system* S, const bx_env_params* env, int64_t n_envs, int32_t n_steps,
+                       const float* qp_in, const float* obs_in, const float* done_in,
+                       const float* steps_in, const uint32_t* rng_in, const bx_policy* policy,
+                       uint64_t seed, uint64_t offset, uint64_t step_stride, const float* eval_in,
+                       float* out, float* eval_out, uint32_t* rng_out, void* stream) {
+  if (!S || !env) return fail("null argument");
+  if (n_steps < 0) return fail("negative n_steps");
+  if (!policy) return fail("null policy");
+  const int64_t A = policy->action_size;
+  PolArgs q{};
+  EvalArgs v{};
+  size_t pol_lds = 0, lds = 0;
+  if (check_env(S, env) || check_draw(S, env, A) || policy_plan(S, env, policy, A, &q, &pol_lds) ||
+      eval_plan(S, env, pol_lds, &v, &lds))
+    return 1;
+  if (n_steps == 0) return 0;
+  if (n_envs > 0 && !obs_in) return fail("null obs_in");
+  if (n_envs > 0 && !eval_out) return fail("null eval_out");
+  q.obs_in = obs_in;
+  q.seed = seed;
+  q.offset = offset;
+  q.step = step_stride;
+  v.in = eval_in;
+  v.out = eval_out;
+  const DrawSpec d{0, 0, 0, 0.f, 0.f, nullptr};
+  return env_step_packed(S, env, n_envs, n_steps, qp_in, done_in, steps_in, rng_in, nullptr, 0, 0,
+                         A, out, rng_out, stream, &d, &q, pol_lds, &v, lds);
+}
+
+int bx_env_eval_packed(bx_system* S, const bx_env_params* env, int64_t n_envs, int32_t n_steps,
+                       const float* qp_in, const float* done_in, const float* steps_in,
+                       const uint32_t* rng_in, const float* act, int64_t act_stride,
+                       int64_t act_step_stride, int64_t act_width, const float* eval_in, float* out,
+                       float* eval_out, uint32_t* rng_out, void* stream) {
+  if (!S || !env) return fail("null argument");
+  if (n_steps < 0) return fail("negative n_steps");
+  EvalArgs v{};
+  size_t lds = 0;
+  if (check_env(S, env) || eval_plan(S, env, step_lds(S), &v, &lds)) return 1;
+  if (n_steps == 0) return 0;
+  if (act_step_stride < 0) return fail("negative action step stride");
+  if (n_envs > 0 && !eval_out) return fail("null eval_out");
+  v.in = eval_in;
+  v.out = eval_out;
+  return env_step_packed(S, env, n_envs, n_steps, qp_in, done_in, steps_in, rng_in, act,
+                         act_stride, act_step_stride, act_width, out, rng_out, stream, nullptr,
+                         nullptr, 0, &v, lds);
 }
 
 int bx_system_info(bx_system* S, int64_t n_envs, const bx_qp* qp, const bx_info* info, void* stream) {

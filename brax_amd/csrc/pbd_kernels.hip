@@ -4726,9 +4726,19 @@ __device__ __forceinline__ float* policy_eval(const PolArgs& Q, const float* W, 
 // LDS: step 0 loads it from Q.obs_in, env_observe writes it there, the
 // AutoReset select overwrites it with first_obs, and each step copies it to
 // its output block
+// EVL (the env_eval kernels, pbd_eval.hip / pbd_eval_open.hip; PK layout): a
+// whole evaluation. EvalWrapper.step's recurrences (wrappers.py:205-208) run
+// per env on lane 0 after each step's scalars are final; the env's M metric
+// sums | reward sum | active_episodes | episode_steps and the step's M metrics
+// stay in LDS (V.words per env, V.lds_off words into the workgroup's LDS):
+// loaded from V.in before step 0 (null: a fresh evaluation), stored to V.out
+// by the last step. Only the last step stores its output block (at the out
+// pointers themselves, no step offset) and the target envs' rng
 template <int L, int MODE, int F, int M, int EK = EK_ANY, bool PK = false, bool ONE = false,
-          bool POL = false>
-__device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q = PolArgs{}) {
+          bool POL = false, bool EVL = false>
+__device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q = PolArgs{},
+                                              const EvalArgs& V = EvalArgs{}) {
+  static_assert(!EVL || (PK && !ONE), "the evaluation kernels run on the packed K-step layout");
   BX_KSTAMP_DECL
   extern __shared__ __attribute__((aligned(16))) float smem[];
   // the packed SINGLE-mode kernels (Env.step's bx_env_step_packed, the
@@ -4842,6 +4852,17 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
     for (int i = lane; i < P.obs_size; i += L) pobs[i] = Q.obs_in[el * P.obs_size + i];
     esync<L>();
   }
+  // EVL: the env's evaluation words and this step's metrics (lane 0 alone
+  // reads and writes them)
+  float *ev = nullptr, *em = nullptr;
+  if constexpr (EVL) {
+    const int nm = P.n_metrics;
+    ev = smem + V.lds_off + le * V.words;
+    em = ev + nm + 3;
+    if (lane == 0)
+      for (int k = 0; k < nm + 3; k++)
+        ev[k] = (V.in && valid) ? V.in[k * A.n_envs + e] : (k == nm + 1 ? 1.f : 0.f);
+  }
   if (!POL && aw > 0 && lane < C) a0 = drw ? draw_at(0, lane < aw ? lane : aw - 1) : (EARLY ? ea0 : arow_g[lane < aw ? lane : aw - 1]);
   BX_PSTAMP(7);
   if constexpr (S) {
@@ -4876,6 +4897,8 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   BX_PSTAMP(8);
   const int nst = ONE ? 1 : (A.n_steps > 1 ? A.n_steps : 1);
   for (int t = 0; t < nst; t++) {
+  // whether this step stores its outputs (EVL: the last one only)
+  const bool last = !EVL || t == nst - 1;
   // (draw mode: the env programs that read the raw row are refused on the
   // host; physics reads the staged row)
   const float* act = (valid && !drw) ? A.act + e * A.act_stride + t * A.act_step : nullptr;
@@ -4895,14 +4918,14 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   float* blk = nullptr;  // PK: this step's output block
   if constexpr (PK) {
     const int64_t B = A.n_envs;
-    blk = A.out.qp.pos.ptr + t * A.out_step;
+    blk = EVL ? A.out.qp.pos.ptr : A.out.qp.pos.ptr + t * A.out_step;
     O.obs = blk + B * H.N * 16;
     O.reward = O.obs + B * P.obs_size;
     O.done = O.reward + B;
     O.steps = O.reward + 2 * B;
     O.truncation = O.reward + 3 * B;
     O.metrics = P.n_metrics > 0 ? O.reward + 4 * B : nullptr;
-    O.rng = A.out.rng ? A.out.rng + t * A.rng_step : nullptr;
+    O.rng = A.out.rng ? A.out.rng + (EVL ? 0 : t * A.rng_step) : nullptr;
   } else {
     O = A.out;
     if (t > 0) {
@@ -5069,7 +5092,7 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
     // (its launch requires fold), so its observation takes the lane's
     // hoisted body, joint and actuator
     env_observe<L, EK>(c, H, E, lane, kind, P.obs_flags, P.obs_size, act, aw,
-                   valid ? (POL ? pobs : O.obs + e * P.obs_size) : nullptr, P.coef, S ? &X.J : nullptr,
+                   (valid && (POL || last)) ? (POL ? pobs : O.obs + e * P.obs_size) : nullptr, P.coef, S ? &X.J : nullptr,
                    (S && !JBK) ? &X.B : nullptr, (S && EK == EK_HUM) ? &X.A : nullptr);
     BX_KSTAMP(12);
     // the Ant kernel's contact cost: each body lane's clipped squares, summed
@@ -5082,7 +5105,7 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
     // reward / done / metrics (lane 0 of the env)
     if (lane == 0 && valid) {
       const float dt = H.dt;
-      float* m = O.metrics ? O.metrics + e * P.n_metrics : nullptr;
+      float* m = EVL ? (P.n_metrics > 0 ? em : nullptr) : (O.metrics ? O.metrics + e * P.n_metrics : nullptr);
       v3 p1 = ld3(E.qp);
       float reward = 0.f;
       if (KIND_IS(BX_ENV_ANT)) {
@@ -5220,7 +5243,7 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
         // one draw per env step (action repeats included), as the reference
         // splits its key once per step
         const uint32_t key = rng_c + (uint32_t)rep;
-        if (rep == reps - 1) O.rng[e] = key + 1u;
+        if (rep == reps - 1 && last) O.rng[e] = key + 1u;
         if (hit != 0.f) {
           float u0 = uniform_at(key, 0, 0.f, 1.f), u1 = uniform_at(key, 1, 0.f, 1.f);
           float rr = P.coef[2] + P.coef[3] * u0;
@@ -5258,7 +5281,7 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
         // sorted: closeToObject, hits, movingObjectToTarget, movingToObject, touchingObject
         if (m) { m[0] = close; m[1] = hit; m[2] = mtt; m[3] = mto; m[4] = touch; }
         const uint32_t key = rng_c + (uint32_t)rep;
-        if (rep == reps - 1) O.rng[e] = key + 1u;
+        if (rep == reps - 1 && last) O.rng[e] = key + 1u;
         if (hit != 0.f) {
           float u0 = uniform_at(key, 0, 0.f, 1.f), u1 = uniform_at(key, 1, 0.f, 1.f);
           float u2 = uniform_at(key, 2, 0.f, 1.f);
@@ -5300,17 +5323,34 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   }
   if (P.auto_reset) reset_now = done != 0.f;
   if (valid) {
-    if (lane == 0) {
+    if (lane == 0 && last) {
       O.reward[e] = reward_sum;
       O.done[e] = done;
       if (O.steps) O.steps[e] = steps;
       if (O.truncation) O.truncation[e] = trunc;
     }
+    if constexpr (EVL) {
+      // EvalWrapper.step on the values just written (steps, done), in its
+      // order: episode_steps, the sums (active is 0 or 1: the product is
+      // exact, a contracted fma gives the same bits), active
+      if (lane == 0) {
+        const int nm = P.n_metrics;
+        const float active = ev[nm + 1];
+        if (active != 0.f) ev[nm + 2] = steps;
+        for (int k = 0; k < nm; k++) ev[k] += em[k] * active;
+        ev[nm] += reward_sum * active;
+        ev[nm + 1] = active * (1.f - done);
+        if (last) {
+          for (int k = 0; k < nm; k++) O.metrics[e * nm + k] = em[k];
+          for (int k = 0; k < nm + 3; k++) V.out[k * A.n_envs + e] = ev[k];
+        }
+      }
+    }
     if (reset_now) {
       for (int b = lane; b < H.N; b += L) {
         float tmp[13];
         load_qp_global(P.first_qp, e, b, tmp);
-        store_out_qp(b, tmp);
+        if (last) store_out_qp(b, tmp);
         // the next step starts from the reset state
         if (t + 1 < nst) {
           float* s = E.qp + b * QP_STRIDE;
@@ -5320,10 +5360,10 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
       }
       for (int i = lane; i < P.obs_size; i += L) {
         const float fo = P.first_obs[e * P.obs_size + i];
-        O.obs[e * P.obs_size + i] = fo;
+        if (last) O.obs[e * P.obs_size + i] = fo;
         if constexpr (POL) pobs[i] = fo;
       }
-    } else {
+    } else if (last) {
       for (int b = lane; b < H.N; b += L) store_out_qp(b, E.qp + b * QP_STRIDE);
       if constexpr (POL)
         for (int i = lane; i < P.obs_size; i += L) O.obs[e * P.obs_size + i] = pobs[i];

@@ -69,6 +69,16 @@ struct PolArgs {
   float min_std;
   uint64_t seed, offset, step;
 };
+// the evaluation kernels' sums (bx_env_eval_policy / bx_env_eval_packed):
+// (M + 3, B) float32, rows = the M metric sums in the env's metric order, the
+// reward sum, active_episodes, episode_steps. On chip each env of the
+// workgroup holds `words` floats (those M + 3 and the step's M metrics)
+// starting lds_off words into the workgroup's LDS
+struct EvalArgs {
+  const float* in;  // null: a fresh evaluation (zero sums, active 1, steps 0)
+  float* out;       // may be `in`
+  int32_t lds_off, words;
+};
 struct InfoArgs {
   const uint32_t* blob;
   int64_t n_envs;
@@ -131,6 +141,14 @@ hipError_t launch_env_policy_single(int L, int feat, int gw, int tpb, int64_t n_
 hipError_t launch_normal_slabs(float* out, int64_t slab_n, int64_t n_slabs, uint64_t seed,
                                uint64_t offset, uint64_t slab_stride, const int64_t* epoch,
                                uint64_t epoch_stride, hipStream_t s);
+// whole evaluations (env_step_body's EVL; SINGLE mode only): the policy form
+// (pbd_eval.hip, launch_env_policy_single's selection) and the open-loop form
+// (pbd_eval_open.hip, launch_env_step_single's selection for a K-step launch)
+hipError_t launch_env_eval_policy(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
+                                  hipStream_t s, const EnvArgs& a, const PolArgs& q,
+                                  const EvalArgs& v, int fold);
+hipError_t launch_env_eval_open(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
+                                hipStream_t s, const EnvArgs& a, const EvalArgs& v, int fold);
 // MULTI-mode step kernel (large pbd scenes, L = 128 or 256 threads per env;
 // jh: the joint halves)
 hipError_t launch_system_step_multi(int L, int jh, int64_t n_envs, size_t lds, hipStream_t s,

@@ -18,6 +18,7 @@ from brax_amd.envs.humanoid import Humanoid
 from brax_amd.envs.humanoid_standup import HumanoidStandup
 from brax_amd.envs.fast import Fast
 from brax_amd.envs.policy import MLPPolicy, PolicyExtras, policy_rollout
+from brax_amd.envs.evaluator import Evaluator, eval_rollout, eval_supported
 
 _envs = {
     'acrobot': Acrobot,

@@ -468,6 +468,40 @@ int bx_env_rollout_policy(bx_system* sys, const bx_env_params* env, int64_t n_en
                           uint64_t step_stride, float* act_out, float* raw_out, float* logp_out,
                           float* out, uint32_t* rng_out, void* stream);
 
+/* Whole evaluation episodes in one launch (the reference's acting.Evaluator
+ * over EvalWrapper, training/acting.py:77-139, envs/wrappers.py:169-203): the
+ * K steps of bx_env_rollout_policy (bx_env_eval_policy) or of
+ * bx_env_rollout_packed (bx_env_eval_packed, step t's actions at act + t *
+ * act_step_stride), with EvalWrapper.step applied per env after every step,
+ * in float32 and in the wrapper's order:
+ *   episode_steps = active != 0 ? steps : episode_steps
+ *   sum[k] += metric[k] * active   (the env's M metrics, then the step's reward)
+ *   active *= 1 - done
+ * steps and done being the values the step writes to its block. The sums stay
+ * on chip for the whole launch and no per-step output is written:
+ *   out      ONE block, n_envs * (N*16 + O + 4 + M) floats: the K-th step's
+ *            qp | obs | reward, done, steps, truncation | metrics;
+ *   eval_in, eval_out  (M + 3, n_envs) float32: rows 0..M-1 the metric sums in
+ *            the env's metric order, row M the reward sum, row M + 1
+ *            active_episodes, row M + 2 episode_steps. They may be the same
+ *            buffer; a null eval_in starts a fresh evaluation (zero sums,
+ *            active 1, steps 0), so an evaluation continues across launches;
+ *   rng_out  (n_envs), the target envs' streams after the K-th step.
+ * bx_env_eval_policy refuses what bx_env_rollout_policy refuses;
+ * bx_env_eval_packed takes every env kind. Both need a SINGLE-mode system and
+ * add 16-byte-rounded 4 * (2 M + 3) bytes per env of the workgroup to its LDS
+ * (within 160 KiB). n_steps = 0 only checks the arguments. */
+int bx_env_eval_policy(bx_system* sys, const bx_env_params* env, int64_t n_envs, int32_t n_steps,
+                       const float* qp_in, const float* obs_in, const float* done_in,
+                       const float* steps_in, const uint32_t* rng_in, const bx_policy* policy,
+                       uint64_t seed, uint64_t offset, uint64_t step_stride, const float* eval_in,
+                       float* out, float* eval_out, uint32_t* rng_out, void* stream);
+int bx_env_eval_packed(bx_system* sys, const bx_env_params* env, int64_t n_envs, int32_t n_steps,
+                       const float* qp_in, const float* done_in, const float* steps_in,
+                       const uint32_t* rng_in, const float* act, int64_t act_stride,
+                       int64_t act_step_stride, int64_t act_width, const float* eval_in, float* out,
+                       float* eval_out, uint32_t* rng_out, void* stream);
+
 /* Batched System.default_qp from per-env joint angles/velocities
  * (B, num_joint_dof) contiguous (system.py:112-242). */
 int bx_system_default_qp(bx_system* sys, int64_t n_envs,
