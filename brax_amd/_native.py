@@ -91,6 +91,7 @@ _SIGS = {
                                C.c_void_p], C.c_int),
     'bx_env_eval_policy': abi.SIGNATURES['bx_env_eval_policy'],
     'bx_env_eval_packed': abi.SIGNATURES['bx_env_eval_packed'],
+    'bx_env_eval_population': abi.SIGNATURES['bx_env_eval_population'],
 }
 
 EXPORTS = tuple(_SIGS)

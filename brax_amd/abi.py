@@ -125,7 +125,22 @@ EVAL_PACKED_ARGS = (
     ('qp_in', _vp), ('done_in', _vp), ('steps_in', _vp), ('rng_in', _vp), ('act', _vp),
     ('act_stride', C.c_int64), ('act_step_stride', C.c_int64), ('act_width', C.c_int64),
     ('eval_in', _vp), ('out', _vp), ('eval_out', _vp), ('rng_out', _vp), ('stream', _vp))
-ARGS = {'bx_env_eval_policy': EVAL_POLICY_ARGS, 'bx_env_eval_packed': EVAL_PACKED_ARGS}
+
+HEADS = {'normal_tanh': 0, 'identity': 1}  # BX_HEAD_NORMAL_TANH / BX_HEAD_IDENTITY
+POP_NO_STAGE = 1  # BX_POP_NO_STAGE
+
+
+class BxPopulation(C.Structure):
+  _fields_ = [('param_stride', C.c_int64), ('head', C.c_int32), ('reward_shift', C.c_float),
+              ('mom_in', C.c_void_p), ('mom_out', C.c_void_p), ('flags', C.c_int32),
+              ('staged', C.c_int32), ('lds_bytes', C.c_int32)]
+
+
+# bx_env_eval_population: bx_env_eval_policy's arguments, then the population
+# struct before the stream
+EVAL_POPULATION_ARGS = EVAL_POLICY_ARGS[:-1] + (('pop', C.POINTER(BxPopulation)), ('stream', _vp))
+ARGS = {'bx_env_eval_policy': EVAL_POLICY_ARGS, 'bx_env_eval_packed': EVAL_PACKED_ARGS,
+        'bx_env_eval_population': EVAL_POPULATION_ARGS}
 SIGNATURES = {name: ([t for _, t in args], C.c_int) for name, args in ARGS.items()}
 
 

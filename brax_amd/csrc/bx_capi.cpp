@@ -1354,7 +1354,8 @@ static int env_step_impl(bx_system* S, const bx_env_params* env, int64_t n_envs,
                          int32_t n_steps, int64_t act_step, int64_t out_step, int64_t rng_step,
                          const DrawSpec* draw = nullptr, bool packed = false,
                          const PolArgs* pol = nullptr, size_t pol_lds = 0,
-                         const EvalArgs* evl = nullptr, size_t evl_lds = 0) {
+                         const EvalArgs* evl = nullptr, size_t evl_lds = 0,
+                         const PopArgs* pop = nullptr) {
   if (!S || !env || !in || !out) return fail("null argument");
   DEVICE_SCOPE(S);
   if (check_env(S, env)) return 1;
@@ -1399,7 +1400,10 @@ static int env_step_impl(bx_system* S, const bx_env_params* env, int64_t n_envs,
     a.act_out = draw->act_out;
   }
   const int fold = S->fold ? (1 | (S->jb ? 2 : 0) | (S->cb ? 4 : 0)) : 0;
-  if (evl && pol)  // (eval_plan admits SINGLE-mode systems only)
+  if (pop)  // (evl_lds: the whole workgroup's, the population's words included)
+    HIP_OK(launch_env_eval_population(S->L, S->feat, S->gw, S->tpb, n_envs, evl_lds, as_stream(stream), a,
+                                      *pol, *evl, *pop, fold));
+  else if (evl && pol)  // (eval_plan admits SINGLE-mode systems only)
     HIP_OK(launch_env_eval_policy(S->L, S->feat, S->gw, S->tpb, n_envs, evl_lds, as_stream(stream), a, *pol,
                                   *evl, fold));
   else if (evl)
@@ -1431,7 +1435,8 @@ static int env_step_packed(bx_system* S, const bx_env_params* env, int64_t n_env
                            int64_t act_step, int64_t act_width, float* out, uint32_t* rng_out,
                            void* stream, const DrawSpec* draw = nullptr,
                            const PolArgs* pol = nullptr, size_t pol_lds = 0,
-                           const EvalArgs* evl = nullptr, size_t evl_lds = 0) {
+                           const EvalArgs* evl = nullptr, size_t evl_lds = 0,
+                           const PopArgs* pop = nullptr) {
   if (!S || !env) return fail("null argument");
   if (n_envs <= 0) {
     if (check_env(S, env)) return 1;
@@ -1467,7 +1472,7 @@ static int env_step_packed(bx_system* S, const bx_env_params* env, int64_t n_env
   // one step's output block: qp | obs | reward, done, steps, truncation | metrics
   const int64_t block = B * (N * 16 + env->obs_size + 4 + env->n_metrics);
   return env_step_impl(S, env, n_envs, &in, act, act_stride, act_width, &o, stream, n_steps,
-                       act_step, block, B, draw, true, pol, pol_lds, evl, evl_lds);
+                       act_step, block, B, draw, true, pol, pol_lds, evl, evl_lds, pop);
 }
 
 int bx_env_step_packed(bx_system* S, const bx_env_params* env, int64_t n_envs,
@@ -1509,8 +1514,11 @@ int bx_env_rollout_random(bx_system* S, const bx_env_params* env, int64_t n_envs
 // launch's dynamic LDS); the parameters are staged while the workgroup stays
 // within a quarter of the compute unit's 160 KiB (the 4,096-env launch's four
 // one-wave workgroups per compute unit stay co-resident)
+// (identity: the population kernels' identity head, the last layer A wide;
+// no_stage: never stage the shared copy, the population's rows differ per env)
 static int policy_plan(const bx_system* S, const bx_env_params* env, const bx_policy* p,
-                       int64_t act_width, PolArgs* Q, size_t* lds) {
+                       int64_t act_width, PolArgs* Q, size_t* lds, bool identity = false,
+                       bool no_stage = false) {
   if (!p) return fail("null policy");
   if (S->mode != 1) return fail("the policy rollout needs a SINGLE-mode system");
   if (!p->params || ((uintptr_t)p->params & 15)) return fail("policy parameters: null or not 16-byte aligned");
@@ -1535,7 +1543,9 @@ static int policy_plan(const bx_system* S, const bx_env_params* env, const bx_po
     wmax = std::max(wmax, w);
   }
   const int last = p->width[p->n_layers - 1];
-  if (last != 2 * A && !(last == A && p->deterministic))
+  if (identity) {
+    if (last != A) return fail("population: the identity head's last layer is action_size wide");
+  } else if (last != 2 * A && !(last == A && p->deterministic))
     return fail("policy: the last layer is 2 x action_size wide (action_size when deterministic)");
   Q->params = p->params;
   Q->mean = p->obs_mean;
@@ -1551,7 +1561,7 @@ static int policy_plan(const bx_system* S, const bx_env_params* env, const bx_po
   const size_t envs = (size_t)(S->tpb / S->L) * (Q->obs_words + 2 * Q->buf_words) * 4;
   const size_t staged = (size_t)((np + 3) & ~(int64_t)3) * 4;
   Q->lds_off = (int32_t)(base / 4);
-  Q->stage = base + envs + staged <= 40 * 1024 ? 1 : 0;
+  Q->stage = (!no_stage && base + envs + staged <= 40 * 1024) ? 1 : 0;
   *lds = base + envs + (Q->stage ? staged : 0);
   if (*lds > 160 * 1024) return fail("policy: the workgroup's LDS exceeds 160 KiB");
   return 0;
@@ -1624,6 +1634,66 @@ int bx_env_eval_policy(bx_system* S, const bx_env_params* env, int64_t n_envs, i
   const DrawSpec d{0, 0, 0, 0.f, 0.f, nullptr};
   return env_step_packed(S, env, n_envs, n_steps, qp_in, done_in, steps_in, rng_in, nullptr, 0, 0,
                          A, out, rng_out, stream, &d, &q, pol_lds, &v, lds);
+}
+
+int bx_env_eval_population(bx_system* S, const bx_env_params* env, int64_t n_envs, int32_t n_steps,
+                           const float* qp_in, const float* obs_in, const float* done_in,
+                           const float* steps_in, const uint32_t* rng_in, const bx_policy* policy,
+                           uint64_t seed, uint64_t offset, uint64_t step_stride,
+                           const float* eval_in, float* out, float* eval_out, uint32_t* rng_out,
+                           bx_population* pop, void* stream) {
+  if (!S || !env) return fail("null argument");
+  if (n_steps < 0) return fail("negative n_steps");
+  if (!policy) return fail("null policy");
+  if (!pop) return fail("null population");
+  if (pop->head != BX_HEAD_NORMAL_TANH && pop->head != BX_HEAD_IDENTITY)
+    return fail("population: unknown head");
+  const int64_t A = policy->action_size;
+  const int64_t stride = pop->param_stride;
+  PolArgs q{};
+  EvalArgs v{};
+  PopArgs n{};
+  size_t pol_lds = 0, ev_lds = 0;
+  if (check_env(S, env) || check_draw(S, env, A) ||
+      policy_plan(S, env, policy, A, &q, &pol_lds, pop->head == BX_HEAD_IDENTITY, stride != 0) ||
+      eval_plan(S, env, pol_lds, &v, &ev_lds))
+    return 1;
+  if (stride != 0 && (stride < q.n_params || (stride & 3)))
+    return fail("population: param_stride must be 0 or a multiple of 4 floats no smaller than n_params (" +
+                std::to_string(q.n_params) + ")");
+  // the population's words past the evaluation's: per env the moments, then
+  // the env's row when every env's fits within policy_plan's 40 KiB
+  const size_t epb = (size_t)(S->tpb / S->L);
+  const size_t base = (ev_lds + 15) & ~(size_t)15;
+  const int mom_words = pop->mom_out ? (2 * env->obs_size + 1 + 3) & ~3 : 0;
+  const int row_words = (q.n_params + 3) & ~3;
+  n.stage = (stride != 0 && !(pop->flags & BX_POP_NO_STAGE) &&
+             base + epb * (size_t)(mom_words + row_words) * 4 <= 40 * 1024) ? 1 : 0;
+  n.lds_off = (int32_t)(base / 4);
+  n.row_off = mom_words;
+  n.words = mom_words + (n.stage ? row_words : 0);
+  const size_t lds = base + epb * (size_t)n.words * 4;
+  if (lds > 160 * 1024) return fail("population: the workgroup's LDS exceeds 160 KiB");
+  pop->staged = n.stage;
+  pop->lds_bytes = (int32_t)lds;
+  if (n_steps == 0) return 0;
+  if (n_envs > 0 && !obs_in) return fail("null obs_in");
+  if (n_envs > 0 && !eval_out) return fail("null eval_out");
+  q.obs_in = obs_in;
+  q.seed = seed;
+  q.offset = offset;
+  q.step = step_stride;
+  if (pop->head == BX_HEAD_IDENTITY) q.det = 1;  // (no noise is drawn; the head returns before reading it)
+  v.in = eval_in;
+  v.out = eval_out;
+  n.mom_in = pop->mom_in;
+  n.mom_out = pop->mom_out;
+  n.param_stride = stride;
+  n.head = pop->head;
+  n.reward_shift = pop->reward_shift;
+  const DrawSpec d{0, 0, 0, 0.f, 0.f, nullptr};
+  return env_step_packed(S, env, n_envs, n_steps, qp_in, done_in, steps_in, rng_in, nullptr, 0, 0,
+                         A, out, rng_out, stream, &d, &q, pol_lds, &v, lds, &n);
 }
 
 int bx_env_eval_packed(bx_system* S, const bx_env_params* env, int64_t n_envs, int32_t n_steps,

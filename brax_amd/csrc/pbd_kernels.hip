@@ -4655,10 +4655,12 @@ __device__ __forceinline__ void pol_layer(const float* W, const float* hin, floa
 // step t's action row of env e (el: e, or 0 past the batch) from its
 // observation row pobs: the actions into the returned buffer's first aw words
 // (every lane of the env calls; the caller fences before reading them)
-template <int L>
+// POP (the population kernels, pbd_pop.hip): head = 1 is the identity head,
+// action = raw = loc: the last layer is aw wide and its outputs are the actions
+template <int L, bool POP = false>
 __device__ __forceinline__ float* policy_eval(const PolArgs& Q, const float* W, const float* pobs,
                                               float* b0, float* b1, int lane, int64_t el, int64_t e,
-                                              bool valid, int t, int aw, int64_t n_envs) {
+                                              bool valid, int t, int aw, int64_t n_envs, int head = 0) {
   const float* hin = pobs;
   if (Q.mean) {
     for (int i = lane; i < Q.width[0]; i += L) {
@@ -4677,6 +4679,10 @@ __device__ __forceinline__ float* policy_eval(const PolArgs& Q, const float* W, 
     esync<L>();
     hin = hout;
     hout = hin == b0 ? b1 : b0;
+  }
+  if constexpr (POP) {
+    // (hin is one of b0 / b1: at least one layer ran)
+    if (head == 1) return const_cast<float*>(hin);
   }
   // the head: hin holds the logits (loc | scale parameter), hout takes the
   // actions (0..aw) and the log-prob terms (aw..2 aw)
@@ -4734,11 +4740,26 @@ __device__ __forceinline__ float* policy_eval(const PolArgs& Q, const float* W, 
 // loaded from V.in before step 0 (null: a fresh evaluation), stored to V.out
 // by the last step. Only the last step stores its output block (at the out
 // pointers themselves, no step offset) and the target envs' rng
+// POP (the population kernels, pbd_pop.hip; implies POL and EVL): one episode
+// per perturbed policy, the env-side half of the reference's ES / ARS
+// run_episode (training/agents/es/train.py:136-164, ars/train.py:106-130).
+// Env e evaluates its own parameter row, Q.params + e * N.param_stride,
+// staged once per launch in the env's own LDS words when N.stage is set, else
+// read from global memory (the same FMA chains either way); head 1 is the
+// identity head; the reward sum takes (reward - N.reward_shift) * active; and
+// the observation moments of running_statistics.update, centred on the
+// policy's obs_mean, stay in LDS (S1 (O) | S2 (O) | count, N.words per env
+// N.lds_off words into the workgroup's LDS, element i on lane i % L): loaded
+// from N.mom_in before step 0, updated before each step's policy evaluation
+// with the env's active flag as the weight, stored to N.mom_out by the last
+// step (null: no moments, no words)
 template <int L, int MODE, int F, int M, int EK = EK_ANY, bool PK = false, bool ONE = false,
-          bool POL = false, bool EVL = false>
+          bool POL = false, bool EVL = false, bool POP = false>
 __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q = PolArgs{},
-                                              const EvalArgs& V = EvalArgs{}) {
+                                              const EvalArgs& V = EvalArgs{},
+                                              const PopArgs& N = PopArgs{}) {
   static_assert(!EVL || (PK && !ONE), "the evaluation kernels run on the packed K-step layout");
+  static_assert(!POP || (POL && EVL), "the population kernels are evaluation kernels with a policy");
   BX_KSTAMP_DECL
   extern __shared__ __attribute__((aligned(16))) float smem[];
   // the packed SINGLE-mode kernels (Env.step's bx_env_step_packed, the
@@ -4840,6 +4861,8 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   if constexpr (POL) {
     float* pa = smem + Q.lds_off;
     pw = Q.params;
+    // (the host stages the shared copy below only when every env reads row 0)
+    if constexpr (POP) pw += el * N.param_stride;
     if (Q.stage) {
       for (int i = threadIdx.x; i < Q.n_params; i += blockDim.x) pa[i] = Q.params[i];
       pw = pa;
@@ -4862,6 +4885,23 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
     if (lane == 0)
       for (int k = 0; k < nm + 3; k++)
         ev[k] = (V.in && valid) ? V.in[k * A.n_envs + e] : (k == nm + 1 ? 1.f : 0.f);
+  }
+  // POP: the env's moments and, when staged, its parameter row
+  float* mom = nullptr;
+  if constexpr (POP) {
+    float* pp = smem + N.lds_off + le * N.words;
+    const int nw = 2 * P.obs_size + 1;
+    if (N.mom_out) {
+      mom = pp;
+      for (int i = lane; i < nw; i += L) mom[i] = (N.mom_in && valid) ? N.mom_in[e * nw + i] : 0.f;
+    }
+    if (N.stage) {
+      // (rows are 16-byte aligned and param_stride >= n_params rounded up to 4)
+      float* row = pp + N.row_off;
+      for (int i = lane * 4; i < Q.n_params; i += L * 4) st4a(row + i, ld4a(pw + i));
+      pw = row;
+    }
+    esync<L>();
   }
   if (!POL && aw > 0 && lane < C) a0 = drw ? draw_at(0, lane < aw ? lane : aw - 1) : (EARLY ? ea0 : arow_g[lane < aw ? lane : aw - 1]);
   BX_PSTAMP(7);
@@ -4902,8 +4942,27 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   // (draw mode: the env programs that read the raw row are refused on the
   // host; physics reads the staged row)
   const float* act = (valid && !drw) ? A.act + e * A.act_stride + t * A.act_step : nullptr;
+  if constexpr (POP) {
+    // running_statistics.update's weighted sums of the row the policy is about
+    // to read, the weight the env's active flag before this step (0 or 1, so
+    // a contracted fma gives the bits of multiply-then-add); d * d rounds on
+    // its own
+    if (mom) {
+      const int no = P.obs_size;
+      const float w = ev[P.n_metrics + 1];
+      for (int i = lane; i < no; i += L) {
+        const float o = pobs[i];
+        const float d = Q.mean ? o - Q.mean[i] : o;
+        float q = d * d;
+        asm("" : "+v"(q));
+        mom[i] += w * d;
+        mom[no + i] += w * q;
+      }
+      if (lane == 0) mom[2 * no] += w;
+    }
+  }
   if constexpr (POL) {
-    pact = policy_eval<L>(Q, pw, pobs, pb0, pb1, lane, el, e, valid, t, aw, A.n_envs);
+    pact = policy_eval<L, POP>(Q, pw, pobs, pb0, pb1, lane, el, e, valid, t, aw, A.n_envs, POP ? N.head : 0);
     esync<L>();
   } else if (t > 0) {
     if (drw) {
@@ -5338,12 +5397,19 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
         const float active = ev[nm + 1];
         if (active != 0.f) ev[nm + 2] = steps;
         for (int k = 0; k < nm; k++) ev[k] += em[k] * active;
-        ev[nm] += reward_sum * active;
+        if constexpr (POP) ev[nm] += (reward_sum - N.reward_shift) * active;
+        else ev[nm] += reward_sum * active;
         ev[nm + 1] = active * (1.f - done);
         if (last) {
           for (int k = 0; k < nm; k++) O.metrics[e * nm + k] = em[k];
           for (int k = 0; k < nm + 3; k++) V.out[k * A.n_envs + e] = ev[k];
         }
+      }
+    }
+    if constexpr (POP) {
+      if (last && mom) {
+        const int nw = 2 * P.obs_size + 1;
+        for (int i = lane; i < nw; i += L) N.mom_out[e * nw + i] = mom[i];
       }
     }
     if (reset_now) {

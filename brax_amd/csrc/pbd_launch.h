@@ -79,6 +79,19 @@ struct EvalArgs {
   float* out;       // may be `in`
   int32_t lds_off, words;
 };
+// the population kernels' extras (bx_env_eval_population, pbd_pop.hip): env e
+// evaluates the parameter row at PolArgs.params + e * param_stride (0: one
+// shared row). On chip each env of the workgroup holds `words` floats starting
+// lds_off words into the workgroup's LDS: the observation moments S1 (O) |
+// S2 (O) | count (mom_out non-null), then at row_off the env's staged row
+// (stage != 0: n_params words, padded to 4)
+struct PopArgs {
+  const float* mom_in;  // (B, 2 O + 1) or null (zeros)
+  float* mom_out;       // may be mom_in; null: no moments
+  int64_t param_stride;
+  int32_t head, stage, lds_off, words, row_off;
+  float reward_shift;
+};
 struct InfoArgs {
   const uint32_t* blob;
   int64_t n_envs;
@@ -149,6 +162,11 @@ hipError_t launch_env_eval_policy(int L, int feat, int gw, int tpb, int64_t n_en
                                   const EvalArgs& v, int fold);
 hipError_t launch_env_eval_open(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
                                 hipStream_t s, const EnvArgs& a, const EvalArgs& v, int fold);
+// one episode per perturbed policy (env_step_body's POP; pbd_pop.hip,
+// launch_env_policy_single's selection)
+hipError_t launch_env_eval_population(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
+                                      hipStream_t s, const EnvArgs& a, const PolArgs& q,
+                                      const EvalArgs& v, const PopArgs& n, int fold);
 // MULTI-mode step kernel (large pbd scenes, L = 128 or 256 threads per env;
 // jh: the joint halves)
 hipError_t launch_system_step_multi(int L, int jh, int64_t n_envs, size_t lds, hipStream_t s,

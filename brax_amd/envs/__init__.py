@@ -19,6 +19,8 @@ from brax_amd.envs.humanoid_standup import HumanoidStandup
 from brax_amd.envs.fast import Fast
 from brax_amd.envs.policy import MLPPolicy, PolicyExtras, policy_rollout
 from brax_amd.envs.evaluator import Evaluator, eval_rollout, eval_supported
+from brax_amd.envs.population import (PolicyPopulation, PopulationResult, population_rollout,
+                                      population_supported, update_running_statistics)
 
 _envs = {
     'acrobot': Acrobot,

@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from brax_amd import _native
+from brax_amd import _native, abi
 from brax_amd.base import PackedQP
 from brax_amd.envs import wrappers
 from brax_amd.envs.env import State, _f32, _Metrics
@@ -69,7 +69,8 @@ def eval_supported(env, policy=None) -> Optional[str]:
   checks only, no launch)."""
   inner = _peel(env)
   if policy is not None:
-    why = fused_supported(inner, policy)
+    # (an identity head goes to the population kernel, one shared row)
+    why = fused_supported(inner, policy, trajectory=policy.head == 'normal_tanh')
     if why is not None:
       return why
   try:
@@ -79,7 +80,13 @@ def eval_supported(env, policy=None) -> Optional[str]:
   p = u._params(opts, None, None)  # pylint: disable=protected-access
   p.auto_reset = 0
   lib = _native.lib()
-  if policy is not None:
+  if policy is not None and policy.head != 'normal_tanh':
+    desc = policy.descriptor(u.action_size)
+    pop = abi.BxPopulation(head=abi.HEADS[policy.head])
+    rc = lib.bx_env_eval_population(u.sys._h, C.byref(p), 0, 0, None, None, None, None, None,  # pylint: disable=protected-access
+                                    C.byref(desc), 0, 0, 0, None, None, None, None,
+                                    C.byref(pop), None)
+  elif policy is not None:
     desc = policy.descriptor(u.action_size)
     rc = lib.bx_env_eval_policy(u.sys._h, C.byref(p), 0, 0, None, None, None, None, None,  # pylint: disable=protected-access
                                 C.byref(desc), 0, 0, 0, None, None, None, None, None)
@@ -179,10 +186,18 @@ def eval_rollout(env, state: State, k: Optional[int] = None, policy: Optional[ML
     if tuple(obs_in.shape) != (B, O):
       raise ValueError(f'state.obs {tuple(obs_in.shape)} != ({B}, {O})')
     desc = policy.descriptor(A)
-    _native.check(lib.bx_env_eval_policy(
-        u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), obs_in.data_ptr(), done_in.data_ptr(),  # pylint: disable=protected-access
-        ptr(steps_in), ptr(rng_in), C.byref(desc), seed, offset, stride, ev.data_ptr(),
-        out.data_ptr(), ev.data_ptr(), ptr(rng_out), _stream(dev.index)))
+    if policy.head != 'normal_tanh':
+      # ARS's policy: the population kernel with one shared row, no moments
+      pop = abi.BxPopulation(head=abi.HEADS[policy.head])
+      _native.check(lib.bx_env_eval_population(
+          u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), obs_in.data_ptr(), done_in.data_ptr(),  # pylint: disable=protected-access
+          ptr(steps_in), ptr(rng_in), C.byref(desc), seed, offset, stride, ev.data_ptr(),
+          out.data_ptr(), ev.data_ptr(), ptr(rng_out), C.byref(pop), _stream(dev.index)))
+    else:
+      _native.check(lib.bx_env_eval_policy(
+          u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), obs_in.data_ptr(), done_in.data_ptr(),  # pylint: disable=protected-access
+          ptr(steps_in), ptr(rng_in), C.byref(desc), seed, offset, stride, ev.data_ptr(),
+          out.data_ptr(), ev.data_ptr(), ptr(rng_out), _stream(dev.index)))
   else:
     act = actions
     if type(act) is not torch.Tensor or act.dtype != torch.float32 or act.device != dev:
@@ -223,7 +238,7 @@ def _chained(env, state, policy, actions, K, seed, offset, step_stride):
   policy.for_actions(A)
   stride = 2 * B * A if step_stride is None else int(step_stride)
   eps = torch.zeros((K, B, A), dtype=torch.float32, device=dev)
-  if not policy.deterministic:
+  if not policy.deterministic and policy.head == 'normal_tanh':  # (an identity head draws none)
     for t in range(K):
       normal_slabs(eps[t], B * A, 1, seed, offset + t * stride, 0)
   for t in range(K):

@@ -60,12 +60,20 @@ class MLPPolicy:
     obs_mean, obs_std: optional (obs_size,) normalisation, x = (obs - mean) / std.
     min_std: the scale's floor, scale = softplus(s) + min_std.
     deterministic: act at the mode (raw = loc).
+    head: 'normal_tanh' (above) or 'identity': action = raw = the last
+      layer's output, `action_size` wide, no tanh, no scale half, no noise
+      (ARS's `obs @ W`; a zero bias expresses a bias-free matrix). The
+      evaluation and population kernels take it; the trajectory kernel of
+      `policy_rollout` does not.
   """
 
   def __init__(self, layers, activation='swish', obs_mean=None, obs_std=None, min_std=1e-3,
-               deterministic=False, device=None):
+               deterministic=False, device=None, head='normal_tanh'):
     if activation not in _ACTIVATIONS:
       raise ValueError(f'activation {activation!r} not in {sorted(_ACTIVATIONS)}')
+    if head not in abi.HEADS:
+      raise ValueError(f'head {head!r} not in {sorted(abi.HEADS)}')
+    self.head = head
     if (obs_mean is None) != (obs_std is None):
       raise ValueError('obs_mean and obs_std go together')
     self.device = torch.device('cpu' if device is None else device)
@@ -141,6 +149,8 @@ class MLPPolicy:
   @property
   def action_size(self):
     last = self.sizes[-1][1]
+    if self.head == 'identity':
+      return last
     return last // 2 if last % 2 == 0 and not self._loc_only() else last
 
   def _loc_only(self):
@@ -151,7 +161,11 @@ class MLPPolicy:
     """Checks the head against an env's action size; a deterministic policy
     may be `a` wide (no scale half)."""
     last = self.sizes[-1][1]
-    if last == 2 * a:
+    if self.head == 'identity':
+      if last != a:
+        raise ValueError(f'the last layer is {last} wide: the identity head wants {a}')
+      self._a = a
+    elif last == 2 * a:
       self._a = None
     elif last == a and self.deterministic:
       self._a = a
@@ -175,6 +189,8 @@ class MLPPolicy:
       if k + 1 < len(ls):
         x = fn(x)
     logits = x
+    if self.head == 'identity':
+      return logits, logits, torch.zeros(logits.shape[:-1], dtype=dt, device=logits.device), logits
     if self._loc_only():
       loc, scale = logits, torch.ones_like(logits)
     else:
@@ -243,13 +259,17 @@ def _extras(extras, K, B, A, dev):
   return extras
 
 
-def fused_supported(env, policy) -> Optional[str]:
+def fused_supported(env, policy, trajectory: bool = True) -> Optional[str]:
   """None when `bx_env_rollout_policy` takes this env and policy, else the
-  library's reason (a zero-step call: argument checks only, no launch)."""
+  library's reason (a zero-step call: argument checks only, no launch).
+  `trajectory=False` makes only the checks every policy kernel shares (the
+  evaluation and population kernels probe their own entry points after it)."""
   try:
     u, opts = chain_options(env)
   except NotImplementedError as e:
     return str(e)
+  if trajectory and policy.head != 'normal_tanh':
+    return f'the trajectory kernel has no {policy.head} head'
   try:
     desc = policy.descriptor(u.action_size)
   except (ValueError, NotImplementedError) as e:
@@ -258,6 +278,8 @@ def fused_supported(env, policy) -> Optional[str]:
     return f'the policy lives on {policy.params.device}, the env on {u.sys.device}'
   if policy.obs_size != u.obs_size:
     return f'the policy reads {policy.obs_size} observations, the env writes {u.obs_size}'
+  if not trajectory:
+    return None
   p = u._params(opts, None, None)  # pylint: disable=protected-access
   p.auto_reset = 0
   lib = _native.lib()
@@ -366,7 +388,7 @@ def _chained(env, state, policy, K, seed, offset, step_stride):
   policy.for_actions(A)
   stride = 2 * B * A if step_stride is None else int(step_stride)
   eps = torch.zeros((K, B, A), dtype=torch.float32, device=dev)
-  if not policy.deterministic:
+  if not policy.deterministic and policy.head == 'normal_tanh':  # (an identity head draws none)
     for t in range(K):
       normal_slabs(eps[t], B * A, 1, seed, offset + t * stride, 0)
   acts, raws, lps, steps = [], [], [], []

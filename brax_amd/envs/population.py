@@ -1,0 +1,411 @@
+"""One episode per perturbed policy in ONE launch: the env-side half of the
+reference's evolution agents.
+
+ES (`brax/training/agents/es/train.py:136-164`) and ARS
+(`training/agents/ars/train.py:106-130`) evaluate `2 x population` perturbed
+copies of one policy, env i running copy i for a whole episode, and keep two
+things: `cumulative_reward += (reward - reward_shift) * active` with `active
+*= 1 - done`, and the per-step `(obs, active)` pairs for
+`running_statistics.update(..., weights=active)`. `population_rollout` is that
+`run_episode` through `bx_env_eval_population`: env e reads its own parameter
+row, the sums and the observation moments stay on chip, and the launch writes
+one state block, `M + 3` floats and `2 O + 1` moment words per env, whatever K
+is. The optimiser halves (fitness shaping, top directions, Adam) stay with the
+caller.
+
+`PolicyPopulation` owns the `(n_members, stride)` parameter rows and writes
+the perturbations from the counter RNG, so the caller's update regenerates the
+noise (`noise`) instead of keeping it. `update_running_statistics` finishes the
+normaliser's update from the on-chip moments.
+"""
+import copy
+import ctypes as C
+import dataclasses
+from typing import Any, Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from brax_amd import _native, abi
+from brax_amd.base import PackedQP
+from brax_amd.envs import wrappers
+from brax_amd.envs.env import State, _f32, _Metrics
+from brax_amd.envs.policy import (_ACTIVATIONS, MLPPolicy, _packed, _stream, fused_supported,
+                                  normal_slabs)
+from brax_amd.envs.rollout import chain_options
+
+
+class PolicyPopulation:
+  """`n_members` parameter rows of one `MLPPolicy` shape in one device buffer.
+
+  `rows` is `(n_members, stride)` float32, `stride` the policy's `n_params`
+  rounded up to 4 floats (each row 16-byte aligned, `MLPPolicy.params`'
+  layout); the policy's own buffer is theta, the point the rows perturb.
+  """
+
+  def __init__(self, policy: MLPPolicy, n_members: int):
+    if int(n_members) < 1:
+      raise ValueError(f'n_members must be >= 1, got {n_members}')
+    self.policy = policy
+    self.n_members = int(n_members)
+    self.n_params = policy.params.numel()
+    self.stride = (self.n_params + 3) & ~3
+    self.rows = torch.zeros((self.n_members, self.stride), dtype=torch.float32,
+                            device=policy.params.device)
+    self.rows[:, :self.n_params] = policy.params
+
+  def set_(self, rows):
+    """Explicit rows, `(n_members, n_params)`, into the same buffer."""
+    rows = torch.as_tensor(rows, dtype=torch.float32)
+    if tuple(rows.shape) != (self.n_members, self.n_params):
+      raise ValueError(f'rows {tuple(rows.shape)} != ({self.n_members}, {self.n_params})')
+    self.rows[:, :self.n_params].copy_(rows)
+    return self
+
+  def _directions(self, antithetic):
+    if not antithetic:
+      return self.n_members
+    if self.n_members % 2:
+      raise ValueError(f'antithetic perturbations need an even n_members, got {self.n_members}')
+    return self.n_members // 2
+
+  def noise(self, seed: int, offset: int = 0, antithetic: bool = True):
+    """The eps of `perturb_(sigma, seed, offset, antithetic)`, regenerated:
+    `(P, n_params)` float32, eps[p, j] = N(seed, offset + 2 (p * n_params +
+    j)) of `bx_normal_slabs`."""
+    P = self._directions(antithetic)
+    eps = torch.empty((P, self.n_params), dtype=torch.float32, device=self.rows.device)
+    normal_slabs(eps, P * self.n_params, 1, int(seed), int(offset), 0)
+    return eps
+
+  def perturb_(self, sigma: float, seed: int, offset: int = 0, antithetic: bool = True):
+    """Rows 0..P-1 = theta + sigma eps and, antithetic, rows P..2P-1 = theta -
+    sigma eps (the reference's `add_noise` and concatenate; otherwise all n
+    rows take theta + sigma eps), each one float32 rounding of the float64
+    expression."""
+    P = self._directions(antithetic)
+    step = float(sigma) * self.noise(seed, offset, antithetic).to(torch.float64)
+    theta = self.policy.params.to(torch.float64)
+    self.rows[:P, :self.n_params] = (theta + step).to(torch.float32)
+    if antithetic:
+      self.rows[P:, :self.n_params] = (theta - step).to(torch.float32)
+    return self
+
+  def member(self, i: int) -> MLPPolicy:
+    """An `MLPPolicy` over row i (a view: it sees later `set_` / `perturb_`)."""
+    if not 0 <= int(i) < self.n_members:
+      raise IndexError(f'member {i} of {self.n_members}')
+    m = copy.copy(self.policy)
+    m.params = self.rows[int(i), :self.n_params]
+    return m
+
+
+@dataclasses.dataclass(frozen=True)
+class PopulationResult:
+  """What `run_episode` keeps, per env: `scores` (B,) the shifted reward sum,
+  `active`, `episode_steps`, `metric_sums` {key: (B,)} (`EvalWrapper`'s), and
+  the observation moments `obs_s1`, `obs_s2` (B, O), `obs_count` (B,) (None
+  with `moments=False`). `eval_buf` (M + 3, B) and `mom_buf` (B, 2 O + 1) are
+  the launch's buffers (the fields above are views of them); `staged` tells
+  whether each env's row was copied to LDS (None on the chained path)."""
+  scores: Any
+  active: Any
+  episode_steps: Any
+  metric_sums: Dict[str, Any]
+  obs_s1: Any
+  obs_s2: Any
+  obs_count: Any
+  metric_keys: Tuple[str, ...]
+  eval_buf: Any
+  mom_buf: Any
+  staged: Optional[bool] = None
+
+
+def _result(ev, mom, keys, O, staged=None):
+  M = len(keys)
+  return PopulationResult(
+      scores=ev[M], active=ev[M + 1], episode_steps=ev[M + 2],
+      metric_sums={k: ev[i] for i, k in enumerate(keys)},
+      obs_s1=None if mom is None else mom[:, :O], obs_s2=None if mom is None else mom[:, O:2 * O],
+      obs_count=None if mom is None else mom[:, 2 * O], metric_keys=tuple(keys), eval_buf=ev,
+      mom_buf=mom, staged=staged)
+
+
+def _split(population):
+  """(policy, rows or None): an `MLPPolicy` is a population of one shared row."""
+  if isinstance(population, PolicyPopulation):
+    return population.policy, population
+  if isinstance(population, MLPPolicy):
+    return population, None
+  raise ValueError(f'population must be a PolicyPopulation or an MLPPolicy, got {type(population).__name__}')
+
+
+def _inner(env):
+  return env.env if isinstance(env, wrappers.EvalWrapper) else env
+
+
+def population_supported(env, population, param_stride: Optional[int] = None,
+                         head: Optional[str] = None) -> Optional[str]:
+  """None when `bx_env_eval_population` takes this env and population, else
+  the library's reason (a zero-step call: argument checks only, no launch).
+  `param_stride` / `head` override the population's (the library's refusals)."""
+  policy, pop = _split(population)
+  inner = _inner(env)
+  why = fused_supported(inner, policy, trajectory=False)
+  if why is not None:
+    return why
+  u, opts = chain_options(inner)
+  p = u._params(opts, None, None)  # pylint: disable=protected-access
+  p.auto_reset = 0
+  desc = policy.descriptor(u.action_size)
+  if pop is not None:
+    desc.params = pop.rows.data_ptr()
+  stride = (0 if pop is None else pop.stride) if param_stride is None else int(param_stride)
+  arg = abi.BxPopulation(param_stride=stride,
+                         head=abi.HEADS[policy.head] if head is None else abi.HEADS.get(head, -1))
+  lib = _native.lib()
+  rc = lib.bx_env_eval_population(u.sys._h, C.byref(p), 0, 0, None, None, None, None, None,  # pylint: disable=protected-access
+                                  C.byref(desc), 0, 0, 0, None, None, None, None, C.byref(arg),
+                                  None)
+  return None if rc == 0 else lib.bx_last_error().decode()
+
+
+def population_rollout(env, state: State, population, k: Optional[int] = None, seed: int = 0,
+                       offset: int = 0, reward_shift: float = 0.0, moments: bool = True,
+                       carry: Optional[PopulationResult] = None, fused: Optional[bool] = None,
+                       stage: Optional[bool] = None, out: Optional[torch.Tensor] = None,
+                       eval_out: Optional[torch.Tensor] = None,
+                       mom_out: Optional[torch.Tensor] = None) -> Tuple[State, PopulationResult]:
+  """K steps of a batch whose env e acts with member e of `population`.
+
+  action_t[e] = member_e(obs_t[e], eps_t[e]) with `policy_rollout`'s noise
+  (eps of step t, env e, action a = N(seed, offset + t * 2 B A + (e A + a) *
+  2); an identity head draws none), then `env.step`; per env, in float32 and
+  in this order, with a = active before the step and o the row the policy
+  reads: S1 += a (o - mean), S2 += a (o - mean)^2, count += a (mean: the
+  policy's `obs_mean`, or 0); after the step `EvalWrapper.step`'s recurrences
+  with the reward sum taking `(reward - reward_shift) * active`.
+
+  Args:
+    env: a batched env (an `EvalWrapper` on top is looked through).
+    population: a `PolicyPopulation` of B members, or an `MLPPolicy` (every
+      env shares its row).
+    k: the steps; None takes `episode_length // action_repeat` of the env's
+      `EpisodeWrapper`.
+    moments: False keeps no observation moments.
+    carry: an earlier call's result to continue from (None: a fresh run).
+    fused: None takes the kernel where the library allows it, else the chained
+      path (a batched `torch.bmm` forward, `env.step`, the recurrences in
+      torch); True raises NotImplementedError where the kernel refuses; False
+      forces the chained path.
+    stage: False reads the rows from global memory whatever the LDS budget
+      (the same bits; None: the library's plan).
+    out, eval_out, mom_out: optional buffers for the fused launch to write: a
+      flat contiguous float32 of B * (N*16 + O + 4 + M) floats, a contiguous
+      float32 (M + 3, B) and a contiguous float32 (B, 2 O + 1); the result's
+      tensors are views of them.
+  Returns:
+    (the state after the K-th step, the PopulationResult).
+  """
+  policy, pop = _split(population)
+  inner = _inner(env)
+  if k is None:
+    w = inner
+    while isinstance(w, wrappers.Wrapper) and not isinstance(w, wrappers.EpisodeWrapper):
+      w = w.env
+    if not isinstance(w, wrappers.EpisodeWrapper):
+      raise ValueError('k=None needs an EpisodeWrapper in the chain')
+    k = w.episode_length // w.action_repeat
+  K = int(k)
+  if K < 1:
+    raise ValueError(f'k must be >= 1, got {k}')
+  B = state.obs.shape[0]
+  if pop is not None and pop.n_members != B:
+    raise ValueError(f'the population holds {pop.n_members} members, the state {B} envs')
+  why = None if fused is False else population_supported(env, population)
+  if fused is True and why is not None:
+    raise NotImplementedError(f'no fused population rollout: {why}')
+  if fused is False or why is not None:
+    return _chained(inner, state, policy, pop, K, seed, offset, reward_shift, moments, carry)
+  u, opts = chain_options(inner)
+  dev = u.sys.device
+  qbuf = _packed(state, dev)
+  A = u.action_size
+  auto = bool(opts.get('auto_reset'))
+  info_in = state.info
+  first_qp = info_in.get('first_qp') if auto else None
+  first_obs = info_in.get('first_obs') if auto else None
+  if auto and (first_qp is None or first_obs is None):
+    raise ValueError('AutoResetWrapper state lacks first_qp / first_obs')
+  p = u._cached_params(opts, first_qp, first_obs)  # pylint: disable=protected-access
+  done_in = _f32(state.done, dev)
+  steps_in = info_in.get('steps')
+  if steps_in is not None:
+    steps_in = _f32(steps_in, dev)
+  rng_in = info_in.get('rng')
+  if rng_in is None and getattr(u, 'needs_rng', False):
+    rng_in = torch.zeros((B,), dtype=torch.int32, device=dev)
+  keys = tuple(u.metric_keys)
+  N, O, M = u.sys.num_bodies, u.obs_size, len(keys)
+  obs_in = _f32(state.obs, dev)
+  if not obs_in.is_contiguous():
+    obs_in = obs_in.contiguous()
+  if tuple(obs_in.shape) != (B, O):
+    raise ValueError(f'state.obs {tuple(obs_in.shape)} != ({B}, {O})')
+  ev, mom = _fresh(carry, keys, B, O, moments, dev)
+  block = B * (N * 16 + O + 4 + M)
+  for name, buf, shape in (('eval_out', eval_out, (M + 3, B)), ('mom_out', mom_out, (B, 2 * O + 1))):
+    if buf is not None and (tuple(buf.shape) != shape or buf.dtype != torch.float32
+                            or not buf.is_contiguous() or buf.device != dev):
+      raise ValueError(f'{name} must be contiguous float32 {shape} on {dev}')
+  if eval_out is not None:
+    ev = eval_out.copy_(ev)
+  if mom_out is not None and mom is not None:
+    mom = mom_out.copy_(mom)
+  if out is None:
+    out = torch.empty((block,), dtype=torch.float32, device=dev)
+  elif (out.numel() < block or out.dtype != torch.float32 or not out.is_contiguous()
+        or out.device != dev):
+    raise ValueError(f'out must hold {block} contiguous float32 on {dev}')
+  rng_out = torch.empty((B,), dtype=torch.int32, device=dev) if rng_in is not None else None
+  ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+  desc = policy.descriptor(A)
+  if pop is not None:
+    desc.params = pop.rows.data_ptr()
+  arg = abi.BxPopulation(param_stride=0 if pop is None else pop.stride, head=abi.HEADS[policy.head],
+                         reward_shift=float(reward_shift), mom_in=ptr(mom), mom_out=ptr(mom),
+                         flags=abi.POP_NO_STAGE if stage is False else 0)
+  _native.check(_native.lib().bx_env_eval_population(
+      u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), obs_in.data_ptr(), done_in.data_ptr(),  # pylint: disable=protected-access
+      ptr(steps_in), ptr(rng_in), C.byref(desc), int(seed), int(offset), 2 * B * A, ev.data_ptr(),
+      out.data_ptr(), ev.data_ptr(), ptr(rng_out), C.byref(arg), _stream(dev.index)))
+  q, obs, sc, met = torch.split(out[:block], (B * N * 16, B * O, 4 * B, B * M))
+  sc = sc.view(4, B)
+  info = {kk: v for kk, v in info_in.items() if kk != 'eval_metrics'}
+  if p.episode_length > 0:
+    info['steps'] = sc[2]
+    info['truncation'] = sc[3]
+  if rng_out is not None:
+    info['rng'] = rng_out
+  m_in = state.metrics
+  extra = dict(m_in.carried(keys) if type(m_in) is _Metrics else {
+      kk: v for kk, v in m_in.items() if kk not in keys})
+  final = State(qp=PackedQP(q.view(B, N, 16)), obs=obs.view(B, O), reward=sc[0], done=sc[1],
+                metrics=_Metrics(met.view(B, M) if M else None, keys, extra), info=info)
+  return final, _result(ev, mom, keys, O, bool(arg.staged))
+
+
+def _fresh(carry, keys, B, O, moments, dev):
+  """The launch's `(M + 3, B)` and `(B, 2 O + 1)` buffers: copies of the
+  carried ones, or a fresh run's (zero sums, active 1)."""
+  M = len(keys)
+  if carry is not None:
+    if tuple(carry.metric_keys) != tuple(keys) or tuple(carry.eval_buf.shape) != (M + 3, B):
+      raise ValueError('carry does not come from this env and batch')
+    if moments and carry.mom_buf is None:
+      raise ValueError('carry holds no moments')
+    ev = carry.eval_buf.to(dev, torch.float32).clone()
+    mom = carry.mom_buf.to(dev, torch.float32).clone() if moments else None
+    return ev, mom
+  ev = torch.zeros((M + 3, B), dtype=torch.float32, device=dev)
+  ev[M + 1] = 1.
+  mom = torch.zeros((B, 2 * O + 1), dtype=torch.float32, device=dev) if moments else None
+  return ev, mom
+
+
+def forward_rows(policy: MLPPolicy, rows, obs, eps=None):
+  """`policy.forward`'s action with env e's weights read from `rows[e]`
+  (`(B, >= n_params)`; None: the policy's own row for every env): one
+  `torch.bmm` per layer."""
+  if rows is None:
+    return policy.forward(obs, eps)[0]
+  dt = obs.dtype
+  x = obs
+  if policy.obs_mean is not None:
+    x = (x - policy.obs_mean.to(x.device, dt)) / policy.obs_std.to(x.device, dt)
+  fn = _ACTIVATIONS[policy.activation]
+  o = 0
+  for l, (i, n) in enumerate(policy.sizes):
+    w = rows[:, o:o + i * n].reshape(-1, i, n).to(x.device, dt)
+    b = rows[:, o + i * n:o + (i + 1) * n].to(x.device, dt)
+    x = torch.bmm(x[:, None, :], w)[:, 0] + b
+    if l + 1 < len(policy.sizes):
+      x = fn(x)
+    o += (i + 1) * n
+  if policy.head == 'identity':
+    return x
+  if policy._loc_only():  # pylint: disable=protected-access
+    loc, scale = x, torch.ones_like(x)
+  else:
+    loc, s = torch.chunk(x, 2, dim=-1)
+    scale = torch.nn.functional.softplus(s) + policy.min_std
+  if policy.deterministic or eps is None:
+    return torch.tanh(loc)
+  return torch.tanh(loc + scale * eps.to(dt))
+
+
+def _chained(env, state, policy, pop, K, seed, offset, reward_shift, moments, carry):
+  """The same loop through `env.step`, the recurrences in the kernel's order:
+  any env, any chain."""
+  dev = torch.device(state.obs.device)
+  B, A, O = state.obs.shape[0], env.action_size, state.obs.shape[1]
+  policy.for_actions(A)
+  try:
+    keys = tuple(chain_options(env)[0].metric_keys)
+  except NotImplementedError:
+    keys = tuple(sorted(state.metrics.keys()))
+  M = len(keys)
+  ev, mom = _fresh(carry, keys, B, O, moments, dev)
+  rows = None if pop is None else pop.rows
+  stochastic = policy.head == 'normal_tanh' and not policy.deterministic
+  eps = torch.zeros((B, A), dtype=torch.float32, device=dev)
+  shift = torch.tensor(float(reward_shift), dtype=torch.float32, device=dev)
+  mean = None if policy.obs_mean is None else policy.obs_mean.to(dev)
+  zeros = torch.zeros((B,), dtype=torch.float32, device=dev)
+  for t in range(K):
+    obs = state.obs.to(torch.float32)
+    active = ev[M + 1].clone()
+    if mom is not None:
+      d = obs if mean is None else obs - mean
+      mom[:, :O] += active[:, None] * d
+      mom[:, O:2 * O] += active[:, None] * (d * d)
+      mom[:, 2 * O] += active
+    if stochastic:
+      normal_slabs(eps, B * A, 1, int(seed), int(offset) + t * 2 * B * A, 0)
+    state = env.step(state, forward_rows(policy, rows, obs, eps))
+    steps = _f32(state.info.get('steps', zeros), dev)
+    ev[M + 2] = torch.where(active != 0, steps, ev[M + 2])
+    for i, kk in enumerate(keys):
+      ev[i] += _f32(state.metrics[kk], dev) * active
+    ev[M] += (_f32(state.reward, dev) - shift) * active
+    ev[M + 1] = active * (1 - _f32(state.done, dev))
+  return state, _result(ev, mom, keys, O)
+
+
+def update_running_statistics(mean, summed_variance, count, result, std_min: float = 1e-6,
+                              std_max: float = 1e6):
+  """`running_statistics.update` (`acme/running_statistics.py:156-173`) of the
+  normaliser from a result's moments, in float64. The moments are centred on
+  the old mean (the policy's `obs_mean`; zeros when it had none), so with
+  u = sum S1 / count': mean' = mean + u, summed_variance' += sum S2 - u sum S1
+  (= sum a (o - mean)(o - mean')), exactly the reference's update.
+
+  `result`: a `PopulationResult`, or `(obs_s1, obs_s2, obs_count)`. Returns
+  float64 numpy `(mean, summed_variance, count, std)`.
+  """
+  if isinstance(result, PopulationResult):
+    result = (result.obs_s1, result.obs_s2, result.obs_count)
+  s1, s2, n = (np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, np.float64)
+               for x in result)
+  mean = np.asarray(mean, np.float64)
+  summed_variance = np.asarray(summed_variance, np.float64)
+  S1 = s1.reshape(-1, mean.shape[-1]).sum(0)
+  S2 = s2.reshape(-1, mean.shape[-1]).sum(0)
+  step = float(n.sum())
+  new_count = float(count) + step
+  u = S1 / new_count
+  new_mean = mean + u
+  new_sv = summed_variance + (S2 - u * S1)
+  # (the summed variance can get negative by rounding: the std clamps it)
+  std = np.clip(np.sqrt(np.maximum(new_sv, 0.) / new_count), std_min, std_max)
+  return new_mean, new_sv, new_count, std

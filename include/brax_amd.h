@@ -502,6 +502,60 @@ int bx_env_eval_packed(bx_system* sys, const bx_env_params* env, int64_t n_envs,
                        int64_t act_step_stride, int64_t act_width, const float* eval_in, float* out,
                        float* eval_out, uint32_t* rng_out, void* stream);
 
+/* One episode per perturbed policy in one launch: the env-side half of the
+ * reference's evolution agents (ES training/agents/es/train.py:136-164, ARS
+ * training/agents/ars/train.py:106-130, run_episode). bx_env_eval_policy with
+ * `policy` as the shape shared by every member and, from `pop`:
+ *   param_stride  env e evaluates the parameter row at policy->params + e *
+ *            param_stride floats (>= n_params, a multiple of 4; rows in
+ *            bx_policy's layout). 0: every env shares the one row;
+ *   head     BX_HEAD_NORMAL_TANH: bx_policy's head, bit for bit.
+ *            BX_HEAD_IDENTITY: action = raw = loc (ARS's obs @ W; a zero bias
+ *            row expresses a bias-free matrix): the last layer is A wide, no
+ *            noise is drawn and `deterministic` / `min_std` are not read;
+ *   reward_shift  the reward sum becomes sum += (reward - reward_shift) *
+ *            active (0: bx_env_eval_policy's line exactly);
+ *   mom_in, mom_out  (n_envs, 2 O + 1) float32 per env S1 (O) | S2 (O) | count,
+ *            the weighted observation sums of running_statistics.update
+ *            (acme/running_statistics.py:156-173) centred on the policy's
+ *            obs_mean m (0 without one). Before each step's policy
+ *            evaluation, with a the env's active flag before the step and o
+ *            the row the policy is about to read: d = o[i] - m[i], q = d * d,
+ *            S1[i] += a * d, S2[i] += a * q, count += a, one float32 rounding
+ *            each. They may be the same buffer; a null mom_in starts from
+ *            zeros; a null mom_out keeps no moments (and none of their LDS);
+ *   flags    BX_POP_NO_STAGE: read the rows from global memory whatever the
+ *            LDS budget (the same bits; an A/B switch).
+ * Written back on success, n_steps = 0 included: `staged` (1: each env's lanes
+ * copy its row into LDS once per launch; 0: the rows, or the shared row, are
+ * read as bx_env_eval_policy reads its parameters) and `lds_bytes`, the
+ * workgroup's dynamic LDS. Rows are staged when param_stride != 0 and
+ * bx_env_eval_policy's LDS without a staged copy, plus per env of the workgroup
+ * the 16-byte-rounded moments and row, stays within 40 KiB. A non-finite row
+ * or observation poisons its own env alone. Refuses what bx_env_rollout_policy
+ * refuses, a param_stride that is non-zero and below n_params or not a
+ * multiple of 4, an unknown head, and a workgroup LDS beyond 160 KiB.
+ * n_steps = 0 only checks the arguments. (Additive: no ABI bump.) */
+#define BX_HEAD_NORMAL_TANH 0
+#define BX_HEAD_IDENTITY 1
+#define BX_POP_NO_STAGE 1
+typedef struct bx_population {
+  int64_t param_stride;
+  int32_t head; /* BX_HEAD_* */
+  float reward_shift;
+  const float* mom_in;
+  float* mom_out;
+  int32_t flags;     /* BX_POP_* */
+  int32_t staged;    /* out */
+  int32_t lds_bytes; /* out */
+} bx_population;
+int bx_env_eval_population(bx_system* sys, const bx_env_params* env, int64_t n_envs,
+                           int32_t n_steps, const float* qp_in, const float* obs_in,
+                           const float* done_in, const float* steps_in, const uint32_t* rng_in,
+                           const bx_policy* policy, uint64_t seed, uint64_t offset,
+                           uint64_t step_stride, const float* eval_in, float* out, float* eval_out,
+                           uint32_t* rng_out, bx_population* pop, void* stream);
+
 /* Batched System.default_qp from per-env joint angles/velocities
  * (B, num_joint_dof) contiguous (system.py:112-242). */
 int bx_system_default_qp(bx_system* sys, int64_t n_envs,
