@@ -92,6 +92,7 @@ _SIGS = {
     'bx_env_eval_policy': abi.SIGNATURES['bx_env_eval_policy'],
     'bx_env_eval_packed': abi.SIGNATURES['bx_env_eval_packed'],
     'bx_env_eval_population': abi.SIGNATURES['bx_env_eval_population'],
+    'bx_compute_gae': abi.SIGNATURES['bx_compute_gae'],
 }
 
 EXPORTS = tuple(_SIGS)

@@ -139,8 +139,22 @@ class BxPopulation(C.Structure):
 # bx_env_eval_population: bx_env_eval_policy's arguments, then the population
 # struct before the stream
 EVAL_POPULATION_ARGS = EVAL_POLICY_ARGS[:-1] + (('pop', C.POINTER(BxPopulation)), ('stream', _vp))
+
+
+class BxSeq(C.Structure):
+  """One float32 (T, B) array: element (t, e) at ptr[t * time_stride + e *
+  env_stride], strides in elements."""
+  _fields_ = [('ptr', C.c_void_p), ('time_stride', C.c_int64), ('env_stride', C.c_int64)]
+
+
+_seq = C.POINTER(BxSeq)
+COMPUTE_GAE_ARGS = (
+    ('n_steps', C.c_int64), ('n_envs', C.c_int64), ('reward', _seq), ('done', _seq),
+    ('truncation', _seq), ('values', _seq), ('bootstrap', _vp), ('vs', _seq),
+    ('advantages', _seq), ('reward_scaling', C.c_float), ('discount', C.c_float),
+    ('lambda', C.c_float), ('stream', _vp))
 ARGS = {'bx_env_eval_policy': EVAL_POLICY_ARGS, 'bx_env_eval_packed': EVAL_PACKED_ARGS,
-        'bx_env_eval_population': EVAL_POPULATION_ARGS}
+        'bx_env_eval_population': EVAL_POPULATION_ARGS, 'bx_compute_gae': COMPUTE_GAE_ARGS}
 SIGNATURES = {name: ([t for _, t in args], C.c_int) for name, args in ARGS.items()}
 
 

@@ -15,6 +15,7 @@
 #include "pbd_features.h"
 #include "pbd_launch.h"
 #include "pbd_layout.h"
+#include "train_launch.h"
 
 using namespace bx;
 
@@ -1951,6 +1952,46 @@ int bx_normal_slabs(float* out, int64_t slab_n, int64_t n_slabs, uint64_t seed, 
   DeviceScope scope(dev);
   if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
   HIP_OK(launch_normal_slabs(out, slab_n, n_slabs, seed, offset, slab_stride, epoch, epoch_stride, st));
+  return 0;
+}
+
+int bx_compute_gae(int64_t n_steps, int64_t n_envs, const bx_seq* reward, const bx_seq* done,
+                   const bx_seq* truncation, const bx_seq* values, const float* bootstrap,
+                   const bx_seq* vs, const bx_seq* advantages, float reward_scaling, float discount,
+                   float lambda, void* stream) {
+  if (!reward || !done || !truncation || !values || !vs || !advantages) return fail("null argument");
+  if (n_steps < 1) return fail("n_steps must be >= 1");
+  if (n_envs < 0) return fail("negative n_envs");
+  if (n_envs > ((int64_t)1 << 31)) return fail("too many envs for one launch");
+  if (n_envs == 0) return 0;
+  if (!reward->ptr || !done->ptr || !truncation->ptr || !values->ptr || !bootstrap || !vs->ptr ||
+      !advantages->ptr)
+    return fail("null argument");
+  // (a zero stride on an input broadcasts one row or column; on an output
+  // every step or env would write the same element)
+  for (const bx_seq* o : {vs, advantages})
+    if ((n_steps > 1 && o->time_stride == 0) || (n_envs > 1 && o->env_stride == 0))
+      return fail("zero stride on an output");
+  int dev = -1;
+  hipStream_t st = as_stream(stream);
+  if (st) HIP_OK(hipStreamGetDevice(st, &dev));
+  else HIP_OK(hipGetDevice(&dev));
+  DeviceScope scope(dev);
+  if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
+  GaeArgs a{};
+  a.T = n_steps;
+  a.B = n_envs;
+  a.reward = *reward;
+  a.done = *done;
+  a.truncation = *truncation;
+  a.values = *values;
+  a.vs = *vs;
+  a.adv = *advantages;
+  a.bootstrap = bootstrap;
+  a.reward_scaling = reward_scaling;
+  a.discount = discount;
+  a.lambda = lambda;
+  HIP_OK(launch_compute_gae(a, st));
   return 0;
 }
 

@@ -6,8 +6,8 @@ then `env.step` (`brax/training/acting.py:30-73`, `actor_step` /
 of that scan in ONE launch (`bx_env_rollout_policy`): each step's action row
 is the policy's, computed on chip from the observation the previous step
 wrote, with the default PPO head (`ppo/networks.py:62-88`: `networks.MLP`,
-`NormalTanhDistribution`, `make_inference_fn`). Training (losses, optimisers,
-GAE) stays with the caller.
+`NormalTanhDistribution`, `make_inference_fn`). The learner (losses, GAE,
+the PPO loop) is `brax_amd.training`.
 
 `MLPPolicy` owns one packed float32 parameter buffer on the device; the
 kernel reads it at launch, so `load_` (in place, same address) or a replayed
@@ -32,6 +32,24 @@ _ACTIVATIONS = {
     'relu': torch.relu,
     'tanh': torch.tanh,
 }
+
+
+def head_scale(s, min_std):
+  """The NormalTanh head's scale from its parameter half."""
+  return torch.nn.functional.softplus(s) + min_std
+
+
+def tanh_log_det(raw):
+  """log |d tanh(x) / dx| (`TanhBijector.forward_log_det_jacobian`)."""
+  return 2.0 * (math.log(2.0) - raw - torch.nn.functional.softplus(-2.0 * raw))
+
+
+def normal_tanh_log_prob(loc, scale, raw):
+  """Per action: log N(raw; loc, scale) minus the tanh log-det. One copy of
+  the formulae for `MLPPolicy.forward` and the learner (`brax_amd.training`),
+  so the log-prob a loss recomputes is the one the rollout recorded."""
+  z = (raw - loc) / scale
+  return -0.5 * z * z - 0.5 * math.log(2 * math.pi) - torch.log(scale) - tanh_log_det(raw)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -195,16 +213,13 @@ class MLPPolicy:
       loc, scale = logits, torch.ones_like(logits)
     else:
       loc, s = torch.chunk(logits, 2, dim=-1)
-      scale = torch.nn.functional.softplus(s) + self.min_std
+      scale = head_scale(s, self.min_std)
     if self.deterministic or eps is None:
       eps = torch.zeros_like(loc)
     eps = eps.to(dt)
     raw = loc + scale * eps
     action = torch.tanh(raw)
-    z = (raw - loc) / scale
-    logp = (-0.5 * z * z - 0.5 * math.log(2 * math.pi) - torch.log(scale)
-            - 2.0 * (math.log(2.0) - raw - torch.nn.functional.softplus(-2.0 * raw)))
-    return action, raw, logp.sum(-1), logits
+    return action, raw, normal_tanh_log_prob(loc, scale, raw).sum(-1), logits
 
   def descriptor(self, action_size):
     """The `bx_policy` struct over this policy's buffers (they must outlive

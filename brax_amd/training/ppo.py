@@ -1,0 +1,293 @@
+"""PPO on the fused rollouts (`brax/training/agents/ppo/train.py`).
+
+`train` keeps the reference's arguments, asserts, step accounting and
+evaluation schedule on one device. One training step is
+
+* `batch_size * num_minibatches // num_envs` consecutive `policy_rollout`
+  launches of `unroll_length` steps (envs the kernel refuses take its chained
+  path),
+* the normaliser update from the unroll's observations,
+* `num_updates_per_batch` passes, each one permutation of the sequences and
+  `num_minibatches` Adam steps on `ppo_loss`,
+
+after which the policy's weights are copied into the acting `MLPPolicy` in
+place (`load_`: the buffer the rollout kernel reads keeps its address).
+`Learner` holds that state and exposes the three phases; `train` is the loop
+around it with `Evaluator` as the reference's `acting.Evaluator`.
+"""
+import dataclasses
+import time
+from typing import Callable, Optional
+
+import numpy as np
+import torch
+
+from brax_amd.envs import wrappers
+from brax_amd.envs.evaluator import Evaluator
+from brax_amd.envs.policy import MLPPolicy, policy_rollout
+from brax_amd.envs.population import update_running_statistics
+from brax_amd.training import networks as ppo_networks
+from brax_amd.training.losses import Transition, ppo_loss
+
+
+@dataclasses.dataclass(frozen=True)
+class StepAccounting:
+  """`ppo/train.py:103-110`."""
+  env_step_per_training_step: int
+  num_evals_after_init: int
+  num_training_steps_per_epoch: int
+  unrolls_per_training_step: int
+
+
+def step_accounting(num_timesteps: int, num_evals: int, batch_size: int, unroll_length: int,
+                    num_minibatches: int, action_repeat: int, num_envs: int) -> StepAccounting:
+  assert batch_size * num_minibatches % num_envs == 0
+  env_step_per_training_step = batch_size * unroll_length * num_minibatches * action_repeat
+  num_evals_after_init = max(num_evals - 1, 1)
+  # ceil(num_timesteps / (num_evals * env_step_per_training_step))
+  num_training_steps_per_epoch = -(-num_timesteps // (num_evals_after_init
+                                                      * env_step_per_training_step))
+  return StepAccounting(env_step_per_training_step, num_evals_after_init,
+                        num_training_steps_per_epoch, batch_size * num_minibatches // num_envs)
+
+
+class RunningStatistics:
+  """`running_statistics.RunningStatisticsState` for one observation vector:
+  float64 on the host (`update_running_statistics`), with float32 device
+  copies `mean_t` / `std_t` that are updated in place."""
+
+  def __init__(self, size: int, device=None):
+    self.mean = np.zeros(size)
+    self.summed_variance = np.zeros(size)
+    self.count = 0.0
+    self.std = np.ones(size)
+    self.mean_t = torch.zeros((size,), dtype=torch.float32, device=device)
+    self.std_t = torch.ones((size,), dtype=torch.float32, device=device)
+
+  def update(self, obs: torch.Tensor):
+    """`running_statistics.update(state, obs)`, every row of `obs` (..., O)
+    with weight 1: the sums centred on the old mean are taken on `obs`'s
+    device in float64, the O-sized remainder on the host."""
+    rows = obs.reshape(-1, obs.shape[-1])
+    d = rows.double() - torch.as_tensor(self.mean, device=rows.device)
+    self.mean, self.summed_variance, self.count, self.std = update_running_statistics(
+        self.mean, self.summed_variance, self.count,
+        (d.sum(0), (d * d).sum(0), np.array([rows.shape[0]], np.float64)))
+    self.mean_t.copy_(torch.as_tensor(self.mean, dtype=torch.float32))
+    self.std_t.copy_(torch.as_tensor(self.std, dtype=torch.float32))
+    return self
+
+
+def transitions(obs0: torch.Tensor, traj, extras) -> Transition:
+  """One unroll as `acting.actor_step` records it (`training/acting.py:30-50`),
+  leading dimensions `[B, T]` (views of the trajectory, no copies but the
+  observation shift): observation_t is the obs before step t (`obs0`, then the
+  trajectory's), next_observation_t the obs after it (under AutoReset the
+  reset obs), discount = 1 - done."""
+  observation = torch.cat([obs0[None].to(traj.obs.dtype), traj.obs[:-1]], dim=0)
+  t = Transition(observation=observation, action=extras.action, reward=traj.reward,
+                 discount=1 - traj.done, next_observation=traj.obs, truncation=traj.truncation,
+                 raw_action=extras.raw_action, log_prob=extras.log_prob)
+  return t.map(lambda x: x.transpose(0, 1))
+
+
+def _detached(layers):
+  return [(w.detach(), b.detach()) for w, b in layers]
+
+
+class Learner:
+  """The state of one PPO run and the three phases of a training step."""
+
+  def __init__(self, env, num_envs: int, unroll_length: int, batch_size: int,
+               num_minibatches: int, num_updates_per_batch: int, learning_rate: float = 1e-4,
+               entropy_cost: float = 1e-4, discounting: float = 0.9, reward_scaling: float = 1.0,
+               clipping_epsilon: float = 0.3, gae_lambda: float = 0.95,
+               normalize_observations: bool = False, normalize_advantage: bool = True,
+               seed: int = 0, network_factory=ppo_networks.make_ppo_networks, device=None,
+               fused_gae: Optional[bool] = None, action_repeat: int = 1):
+    assert batch_size * num_minibatches % num_envs == 0
+    self.env, self.device = env, torch.device(device)
+    self.action_repeat = int(action_repeat)
+    self.num_envs, self.unroll_length = int(num_envs), int(unroll_length)
+    self.batch_size, self.num_minibatches = int(batch_size), int(num_minibatches)
+    self.num_updates_per_batch = int(num_updates_per_batch)
+    self.unrolls = batch_size * num_minibatches // num_envs
+    self.seed, self.fused_gae = int(seed), fused_gae
+    self.loss_kwargs = dict(entropy_cost=entropy_cost, discounting=discounting,
+                            reward_scaling=reward_scaling, gae_lambda=gae_lambda,
+                            clipping_epsilon=clipping_epsilon,
+                            normalize_advantage=normalize_advantage)
+    O, A = env.observation_size, env.action_size
+    self.policy_layers, self.value_layers = network_factory(O, A, seed=seed, device=self.device)
+    self.normalizer = RunningStatistics(O, self.device) if normalize_observations else None
+    # optax.adam's defaults (eps 1e-8, as torch's)
+    self.optimizer = torch.optim.Adam(
+        ppo_networks.parameters(self.policy_layers, self.value_layers), lr=learning_rate, eps=1e-8)
+    self.actor = self.make_policy(self.params)
+    self._gen = torch.Generator(device=self.device).manual_seed(self.seed)
+    self._noise_offset = 0
+    self.state = None
+    self.env_steps = 0
+
+  @property
+  def params(self):
+    """(normaliser, policy layers, value layers)."""
+    return self.normalizer, self.policy_layers, self.value_layers
+
+  @property
+  def _mean_std(self):
+    return None if self.normalizer is None else (self.normalizer.mean_t, self.normalizer.std_t)
+
+  def make_policy(self, params=None, deterministic: bool = False) -> MLPPolicy:
+    """`make_inference_fn`: an acting `MLPPolicy` from `params` (default: the
+    learner's current ones). It reads the normaliser's device buffers, so a
+    normaliser update reaches it without a copy."""
+    normalizer, policy_layers = (self.params if params is None else params)[:2]
+    kw = {} if normalizer is None else dict(obs_mean=normalizer.mean_t, obs_std=normalizer.std_t)
+    p = MLPPolicy(_detached(policy_layers), activation='swish', deterministic=deterministic,
+                  device=self.device, **kw)
+    if normalizer is not None:  # share, not copy
+      p.obs_mean, p.obs_std = normalizer.mean_t, normalizer.std_t
+    return p
+
+  def reset(self, key):
+    self.state = self.env.reset(key)
+    if self.state.obs.shape[0] != self.num_envs:
+      raise ValueError(f'the env holds {self.state.obs.shape[0]} envs, num_envs is {self.num_envs}')
+    return self.state
+
+  def collect(self) -> Transition:
+    """The unroll phase: `[batch_size * num_minibatches, unroll_length]`
+    transitions from consecutive `policy_rollout` launches."""
+    parts = []
+    A = self.env.action_size
+    for _ in range(self.unrolls):
+      obs0 = self.state.obs
+      self.state, traj, extras = policy_rollout(
+          self.env, self.state, self.actor, self.unroll_length, seed=self.seed,
+          offset=self._noise_offset, fused=None)
+      self._noise_offset += self.unroll_length * 2 * self.num_envs * A
+      parts.append(transitions(obs0, traj, extras))
+    if len(parts) == 1:
+      return parts[0]
+    names = [f.name for f in dataclasses.fields(Transition)]
+    return Transition(**{n: torch.cat([getattr(p, n) for p in parts], dim=0) for n in names})
+
+  def update_normalizer(self, data: Transition):
+    if self.normalizer is not None:
+      self.normalizer.update(data.observation)
+
+  def update(self, data: Transition):
+    """The update phase: `num_updates_per_batch` x `num_minibatches` Adam
+    steps; returns the mean of each loss metric (device tensors)."""
+    n, bs = data.reward.shape[0], self.batch_size
+    A = data.action.shape[-1]
+    sums = {}
+    for _ in range(self.num_updates_per_batch):
+      perm = torch.randperm(n, generator=self._gen, device=self.device)
+      shuffled = data.map(lambda x, perm=perm: x[perm])
+      for m in range(self.num_minibatches):
+        mb = shuffled.map(lambda x, m=m: x[m * bs:(m + 1) * bs])
+        eps = torch.randn((bs, self.unroll_length, A), generator=self._gen, device=self.device)
+        loss, metrics = ppo_loss(self.policy_layers, self.value_layers, self._mean_std, mb, eps,
+                                 fused=self.fused_gae, **self.loss_kwargs)
+        self.optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        self.optimizer.step()
+        for k, v in metrics.items():
+          sums[k] = v.detach() + sums.get(k, 0)
+    self.actor.load_(_detached(self.policy_layers))
+    steps = self.num_updates_per_batch * self.num_minibatches
+    return {k: v / steps for k, v in sums.items()}
+
+  def training_step(self):
+    data = self.collect()
+    self.update_normalizer(data)
+    metrics = self.update(data)
+    self.env_steps += data.reward.numel() * self.action_repeat
+    return metrics
+
+
+def train(environment, num_timesteps: int, episode_length: int, action_repeat: int = 1,
+          num_envs: int = 1, max_devices_per_host: Optional[int] = None,
+          num_eval_envs: int = 128, learning_rate: float = 1e-4, entropy_cost: float = 1e-4,
+          discounting: float = 0.9, seed: int = 0, unroll_length: int = 10, batch_size: int = 32,
+          num_minibatches: int = 16, num_updates_per_batch: int = 2, num_evals: int = 1,
+          normalize_observations: bool = False, reward_scaling: float = 1.0,
+          clipping_epsilon: float = 0.3, gae_lambda: float = 0.95,
+          deterministic_eval: bool = False, network_factory=ppo_networks.make_ppo_networks,
+          progress_fn: Callable[[int, dict], None] = lambda *args: None,
+          normalize_advantage: bool = True, eval_env=None, device=None,
+          fused_gae: Optional[bool] = None):
+  """PPO training; the reference's arguments and defaults
+  (`ppo/train.py:61-86`).
+
+  Args:
+    environment: an env name (created with the Episode / Vector / AutoReset
+      wrappers at `num_envs`), or such a batched env.
+    max_devices_per_host: accepted and ignored (one device).
+    eval_env: with a batched `environment`, the same env batched at
+      `num_eval_envs` (a name is created at both sizes).
+    device: the GPU (default `cuda`).
+    fused_gae: `compute_gae`'s `fused` (None: the kernel).
+  Returns:
+    `(make_policy, params, metrics)`: `make_policy(params, deterministic=False)`
+    gives an `MLPPolicy`; `params` is (the normaliser or None, the policy
+    layers, the value layers); `metrics` the last evaluation's dict with
+    `training/sps` and `training/walltime`.
+  """
+  del max_devices_per_host
+  acct = step_accounting(num_timesteps, num_evals, batch_size, unroll_length, num_minibatches,
+                         action_repeat, num_envs)
+  dev = torch.device('cuda' if device is None else device)
+  if isinstance(environment, str):
+    from brax_amd import envs  # pylint: disable=import-outside-toplevel
+    env = envs.create(environment, episode_length=episode_length, action_repeat=action_repeat,
+                      batch_size=num_envs, device=dev)
+    eval_env = environment if eval_env is None else eval_env
+  else:
+    env = environment
+    if eval_env is None:
+      if num_eval_envs != num_envs:
+        raise ValueError('a batched environment needs eval_env batched at num_eval_envs')
+      eval_env = env
+  learner = Learner(env, num_envs, unroll_length, batch_size, num_minibatches,
+                    num_updates_per_batch, learning_rate=learning_rate, entropy_cost=entropy_cost,
+                    discounting=discounting, reward_scaling=reward_scaling,
+                    clipping_epsilon=clipping_epsilon, gae_lambda=gae_lambda,
+                    normalize_observations=normalize_observations,
+                    normalize_advantage=normalize_advantage, seed=seed,
+                    network_factory=network_factory, device=dev, fused_gae=fused_gae,
+                    action_repeat=action_repeat)
+  key = np.array([0, int(seed)], np.uint32)  # jax.random.PRNGKey(seed) layout
+  key_env, key_eval = wrappers.split_key(key)
+  learner.reset(key_env)
+  eval_policy = learner.make_policy(deterministic=True) if deterministic_eval else learner.actor
+  evaluator = Evaluator(eval_env, eval_policy, num_eval_envs=num_eval_envs,
+                        episode_length=episode_length, action_repeat=action_repeat,
+                        seed=int(wrappers.key_to_seed(key_eval)) & 0x7FFFFFFF, device=dev)
+  metrics = {}
+  if num_evals > 1:
+    metrics = evaluator.run_evaluation(training_metrics={})
+    progress_fn(0, metrics)
+  training_walltime = 0.0
+  for _ in range(acct.num_evals_after_init):
+    t = time.time()
+    sums = {}
+    for _ in range(acct.num_training_steps_per_epoch):
+      for k, v in learner.training_step().items():
+        sums[k] = v + sums.get(k, 0)
+    torch.cuda.synchronize(dev)
+    epoch_training_time = time.time() - t
+    training_walltime += epoch_training_time
+    training_metrics = {
+        'training/sps': (acct.num_training_steps_per_epoch * acct.env_step_per_training_step
+                         / epoch_training_time),
+        'training/walltime': training_walltime,
+        **{f'training/{k}': v / acct.num_training_steps_per_epoch for k, v in sums.items()}}
+    if eval_policy is not learner.actor:
+      eval_policy.load_(_detached(learner.policy_layers))
+    metrics = evaluator.run_evaluation(training_metrics)
+    progress_fn(learner.env_steps, metrics)
+  assert learner.env_steps >= num_timesteps
+  return learner.make_policy, learner.params, metrics

@@ -654,6 +654,45 @@ int bx_normal_slabs(float* out, int64_t slab_n, int64_t n_slabs, uint64_t seed,
                     uint64_t offset, uint64_t slab_stride, const int64_t* epoch,
                     uint64_t epoch_stride, void* stream);
 
+/* A strided view of one fp32 (T, B) sequence array: element (step t, env e)
+ * lives at ptr[t * time_stride + e * env_stride] (strides in elements). The
+ * time-major (K, B) rows of bx_env_rollout_policy's blocks and the reference's
+ * [B, T] arrays both pass without a copy. */
+typedef struct bx_seq {
+  float* ptr;
+  int64_t time_stride;
+  int64_t env_stride;
+} bx_seq;
+
+/* Generalised advantage estimation of a whole (T, B) unroll in one launch:
+ * the reference's `compute_gae` (training/agents/ppo/losses.py:37-93) with the
+ * reward scaling and the termination product of `compute_ppo_loss` (:142-144)
+ * in front of it. `done` stands for 1 - discount_t, so termination = done *
+ * (1 - truncation). One lane per env runs the reverse scan; for t = T-1 .. 0,
+ * with v_next = t == T-1 ? bootstrap[e] : values[t+1], vs_next likewise (the
+ * previous iteration's vs[t]) and acc starting at 0:
+ *   r     = reward[t] * reward_scaling
+ *   term  = done[t] * (1 - truncation[t])
+ *   mask  = 1 - truncation[t]
+ *   g     = discount * (1 - term)
+ *   delta = ((r + g * v_next) - values[t]) * mask
+ *   acc   = delta + ((g * mask) * lambda) * acc
+ *   vs[t] = acc + values[t]
+ *   advantages[t] = ((r + g * vs_next) - values[t]) * mask
+ * in float32, every operation rounded on its own (no fused multiply-add), in
+ * that order: bit for bit what the same lines give as separate elementwise
+ * float32 operations. NaN and Inf propagate as IEEE has them (NaN * 0 is
+ * NaN); a non-finite input of env e reaches no other env's outputs.
+ * bootstrap is (B,) contiguous. The outputs may have any layout but must not
+ * overlap the inputs or each other. n_steps < 1, n_envs < 0, a null pointer
+ * or a zero stride on an output fail; n_envs = 0 launches nothing. No system
+ * handle: the launch goes to the device that owns `stream` (the current
+ * device for NULL). (Additive: no ABI bump.) */
+int bx_compute_gae(int64_t n_steps, int64_t n_envs, const bx_seq* reward, const bx_seq* done,
+                   const bx_seq* truncation, const bx_seq* values, const float* bootstrap,
+                   const bx_seq* vs, const bx_seq* advantages, float reward_scaling,
+                   float discount, float lambda, void* stream);
+
 /*
  * Standalone HBM-streaming phase kernels over a structure-of-arrays batch
  * (the integrator and collider phases benchmarked in isolation).

@@ -1,0 +1,337 @@
+"""`brax_amd.training` without a GPU: the chained `compute_gae` and `ppo_loss`
+against float64 numpy restatements of the reference's
+`training/agents/ppo/losses.py`, the ABI mirror of `bx_compute_gae`, and
+`train`'s argument checks and step accounting."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from brax_amd import _native, abi
+from brax_amd.training import Transition, compute_gae, make_ppo_networks, ppo, ppo_loss
+from brax_amd.training import losses as losses_mod
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _reference_gae(truncation, termination, rewards, values, bootstrap_value, lambda_, discount):
+  """`compute_gae`, losses.py:37-93, restated in numpy (the dtype of its
+  inputs); the scan as a loop from the last step."""
+  truncation_mask = 1 - truncation
+  values_t_plus_1 = np.concatenate([values[1:], bootstrap_value[None]], axis=0)
+  deltas = rewards + discount * (1 - termination) * values_t_plus_1 - values
+  deltas = deltas * truncation_mask
+  acc = np.zeros_like(bootstrap_value)
+  vs_minus_v_xs = np.zeros_like(values)
+  for t in range(values.shape[0] - 1, -1, -1):
+    acc = deltas[t] + discount * (1 - termination[t]) * truncation_mask[t] * lambda_ * acc
+    vs_minus_v_xs[t] = acc
+  vs = vs_minus_v_xs + values
+  vs_t_plus_1 = np.concatenate([vs[1:], bootstrap_value[None]], axis=0)
+  advantages = (rewards + discount * (1 - termination) * vs_t_plus_1 - values) * truncation_mask
+  return vs, advantages
+
+
+def _dyadic_case(T):
+  """B = 3: env 0 terminates, env 1 is truncated (done = truncation = 1), env
+  2 is never done; the event at t = 1 (t = 0 when T = 1). Rewards and values
+  are small multiples of 0.25, so with discount = lambda = 0.5 and
+  reward_scaling = 2 every product and sum below is exact in float32."""
+  k = np.arange(T * 3, dtype=np.float64).reshape(T, 3)
+  reward = ((k * 3) % 7 - 3) * 0.25
+  values = ((k * 5) % 9 - 4) * 0.25
+  bootstrap = np.array([0.75, -1.25, 0.5])
+  done = np.zeros((T, 3))
+  truncation = np.zeros((T, 3))
+  ev = min(1, T - 1)
+  done[ev, 0] = 1
+  done[ev, 1] = truncation[ev, 1] = 1
+  return reward, done, truncation, values, bootstrap, ev
+
+
+@pytest.mark.parametrize('T', [1, 2, 4])
+@pytest.mark.parametrize('lam', [0.5, 0.0])
+def test_chained_gae_equals_the_reference_on_dyadic_inputs(T, lam):
+  reward, done, truncation, values, bootstrap, ev = _dyadic_case(T)
+  discount, scaling = 0.5, 2.0
+  termination = done * (1 - truncation)  # (1 - discount_t) * (1 - truncation), losses.py:144
+  want_vs, want_adv = _reference_gae(truncation, termination, reward * scaling, values, bootstrap,
+                                     lam, discount)
+  # the chosen numbers are exact in float32: the float32 restatement agrees
+  f = np.float32
+  vs32, adv32 = _reference_gae(f(truncation), f(termination), f(reward * scaling), f(values),
+                               f(bootstrap), f(lam), f(discount))
+  assert vs32.dtype == np.float32 and np.array_equal(vs32, want_vs) and np.array_equal(adv32, want_adv)
+  for dtype in (torch.float64, torch.float32):
+    t = lambda a: torch.as_tensor(a, dtype=dtype)  # noqa: E731
+    for flag in (done, termination):  # the plain done flag and the reference's product
+      vs, adv = compute_gae(t(truncation), t(flag), t(reward), t(values), t(bootstrap),
+                            lambda_=lam, discount=discount, reward_scaling=scaling)
+      assert vs.dtype == dtype and not vs.requires_grad and not adv.requires_grad
+      assert np.array_equal(vs.double().numpy(), want_vs)
+      assert np.array_equal(adv.double().numpy(), want_adv)
+  # by hand: the truncated step keeps its value and has no advantage
+  assert want_adv[ev, 1] == 0 and want_vs[ev, 1] == values[ev, 1]
+  if lam == 0.0:
+    # vs = r + g * v_next on the steps that are not masked
+    v_next = np.concatenate([values[1:], bootstrap[None]])
+    g = discount * (1 - termination)
+    keep = truncation == 0
+    assert np.array_equal(want_vs[keep], (reward * scaling + g * v_next)[keep])
+
+
+def test_compute_gae_layouts_and_refusals():
+  reward, done, truncation, values, bootstrap, _ = _dyadic_case(4)
+  t = lambda a: torch.as_tensor(a, dtype=torch.float32)  # noqa: E731
+  base = compute_gae(t(truncation), t(done), t(reward), t(values), t(bootstrap), 0.5, 0.5)
+  # [B, T] views, values that carry a graph, out= buffers
+  bt = [t(a.T.copy()).T for a in (truncation, done, reward)]
+  v = t(values).requires_grad_()
+  out = (torch.full((4, 3), 9.0), torch.full((3, 4), 9.0).T)
+  got = compute_gae(*bt, v, t(bootstrap), 0.5, 0.5, out=out)
+  assert got[0] is out[0] and got[1] is out[1]
+  assert torch.equal(got[0], base[0]) and torch.equal(got[1], base[1]) and not got[0].requires_grad
+  with pytest.raises(NotImplementedError):
+    compute_gae(t(truncation), t(done), t(reward), t(values), t(bootstrap), fused=True)  # CPU
+  with pytest.raises(ValueError):
+    compute_gae(t(truncation), t(done), t(reward), t(values), t(bootstrap)[:2])
+  with pytest.raises(ValueError):
+    compute_gae(t(truncation)[:2], t(done), t(reward), t(values), t(bootstrap))
+
+
+# ---- ppo_loss -------------------------------------------------------------------------------
+
+def _np_swish(x):
+  return x / (1 + np.exp(-x))
+
+
+def _np_mlp(layers, x):
+  for k, (w, b) in enumerate(layers):
+    x = x @ w + b
+    if k + 1 < len(layers):
+      x = _np_swish(x)
+  return x
+
+
+def _np_softplus(x):
+  return np.logaddexp(0.0, x)
+
+
+def _reference_ppo_loss(policy, value, normalizer, d, eps, entropy_cost=1e-4, discounting=0.9,
+                        reward_scaling=1.0, gae_lambda=0.95, clipping_epsilon=0.3,
+                        normalize_advantage=True, min_std=0.001):
+  """`compute_ppo_loss`, losses.py:96-182, with `NormalTanhDistribution`
+  (distribution.py:74-158) and `running_statistics.normalize`, in float64
+  numpy; `d` holds [B, T] arrays."""
+  d = {k: np.swapaxes(v, 0, 1) for k, v in d.items()}  # time first
+  eps = np.swapaxes(eps, 0, 1)
+  norm = (lambda o: o) if normalizer is None else (lambda o: (o - normalizer[0]) / normalizer[1])
+  policy_logits = _np_mlp(policy, norm(d['observation']))
+  baseline = _np_mlp(value, norm(d['observation']))[..., 0]
+  bootstrap_value = _np_mlp(value, norm(d['next_observation'][-1]))[..., 0]
+  rewards = d['reward'] * reward_scaling
+  truncation = d['truncation']
+  termination = (1 - d['discount']) * (1 - truncation)
+  loc, scale = np.split(policy_logits, 2, axis=-1)
+  scale = _np_softplus(scale) + min_std
+  log_det = lambda x: 2.0 * (np.log(2.0) - x - _np_softplus(-2.0 * x))  # noqa: E731
+  log_normalization = 0.5 * np.log(2.0 * np.pi) + np.log(scale)
+  x = d['raw_action']
+  target = (-0.5 * np.square(x / scale - loc / scale) - log_normalization - log_det(x)).sum(-1)
+  vs, advantages = _reference_gae(truncation, termination, rewards, baseline, bootstrap_value,
+                                  gae_lambda, discounting)
+  if normalize_advantage:
+    advantages = (advantages - advantages.mean()) / (advantages.std() + 1e-8)
+  rho_s = np.exp(target - d['log_prob'])
+  s1 = rho_s * advantages
+  s2 = np.clip(rho_s, 1 - clipping_epsilon, 1 + clipping_epsilon) * advantages
+  policy_loss = -np.mean(np.minimum(s1, s2))
+  v_error = vs - baseline
+  v_loss = np.mean(v_error * v_error) * 0.5 * 0.5
+  entropy = ((0.5 + log_normalization) + log_det(eps * scale + loc)).sum(-1)
+  entropy_loss = entropy_cost * -np.mean(entropy)
+  total = policy_loss + v_loss + entropy_loss
+  return {'total_loss': total, 'policy_loss': policy_loss, 'v_loss': v_loss,
+          'entropy_loss': entropy_loss}
+
+
+def _loss_case(seed=0, T=3, B=4, O=5, A=2, hidden=(8,)):
+  g = torch.Generator().manual_seed(seed)
+  r = lambda *s: torch.randn(s, generator=g, dtype=torch.float64)  # noqa: E731
+  policy, value = make_ppo_networks(O, A, hidden, hidden, seed=seed + 1, dtype=torch.float64)
+  with torch.no_grad():  # zero biases would hide a wrong bias path
+    for w, b in policy + value:
+      b.copy_(r(*b.shape) * 0.1)
+  done = (torch.rand((B, T), generator=g) < 0.4).double()
+  truncation = done * (torch.rand((B, T), generator=g) < 0.5).double()
+  data = Transition(observation=r(B, T, O), action=torch.tanh(r(B, T, A)), reward=r(B, T),
+                    discount=1 - done, next_observation=r(B, T, O), truncation=truncation,
+                    raw_action=r(B, T, A), log_prob=r(B, T) * 0.3 - 1.5)
+  normalizer = (r(O) * 0.2, torch.rand((O,), generator=g, dtype=torch.float64) + 0.5)
+  return policy, value, normalizer, data, r(B, T, A)
+
+
+@pytest.mark.parametrize('kw', [
+    {}, {'normalize_advantage': False, 'reward_scaling': 0.1, 'discounting': 0.97},
+    {'entropy_cost': 1e-2, 'gae_lambda': 0.0, 'clipping_epsilon': 0.05}])
+@pytest.mark.parametrize('with_normalizer', [True, False])
+def test_ppo_loss_equals_the_reference_in_float64(kw, with_normalizer):
+  policy, value, normalizer, data, eps = _loss_case()
+  if not with_normalizer:
+    normalizer = None
+  loss, metrics = ppo_loss(policy, value, normalizer, data, eps, **kw)
+  n = lambda t: t.detach().numpy()  # noqa: E731
+  want = _reference_ppo_loss(
+      [(n(w), n(b)) for w, b in policy], [(n(w), n(b)) for w, b in value],
+      None if normalizer is None else (n(normalizer[0]), n(normalizer[1])),
+      {f: n(getattr(data, f)) for f in ('observation', 'reward', 'discount', 'next_observation',
+                                        'truncation', 'raw_action', 'log_prob')}, n(eps), **kw)
+  assert sorted(metrics) == ['entropy_loss', 'policy_loss', 'total_loss', 'v_loss']
+  assert loss is metrics['total_loss'] and loss.dtype == torch.float64
+  for k, w in want.items():
+    got = float(metrics[k].detach())
+    print(f'{k}: got {got!r} want {float(w)!r} rel {abs(got - w) / abs(w):.2e}')
+    # a few hundred float64 roundings; any formula error is many orders larger
+    assert abs(got - w) <= 1e-12 * abs(w), k
+
+
+def test_ppo_loss_gradients():
+  policy, value, normalizer, data, eps = _loss_case(seed=3)
+  params = [t for layers in (policy, value) for wb in layers for t in wb]
+  loss, _ = ppo_loss(policy, value, normalizer, data, eps, normalize_advantage=False)
+  grads = torch.autograd.grad(loss, params)
+  for g_ in grads:
+    assert torch.isfinite(g_).all() and float(g_.abs().max()) > 0
+  # Nothing flows through vs and advantages. The values the GAE call reads are
+  # perturbed by a zero leaf inside that call alone: the leaf receives no
+  # gradient and every policy and value gradient keeps its bits. (A non-zero
+  # perturbation there changes the advantages and with them d loss / d policy,
+  # which is linear in them, so the property is stated at the values given.)
+  leaf = torch.zeros_like(data.reward.T, requires_grad=True)
+  seen = {}
+  real = losses_mod.compute_gae
+
+  def perturbed(**kwargs):
+    kwargs['values'] = kwargs['values'] + leaf
+    seen['vs'], seen['adv'] = real(**kwargs)
+    return seen['vs'], seen['adv']
+  losses_mod.compute_gae = perturbed
+  try:
+    loss2, _ = ppo_loss(policy, value, normalizer, data, eps, normalize_advantage=False)
+  finally:
+    losses_mod.compute_gae = real
+  assert not seen['vs'].requires_grad and not seen['adv'].requires_grad
+  grads2 = torch.autograd.grad(loss2, params + [leaf], allow_unused=True)
+  assert grads2[-1] is None
+  assert torch.equal(loss2, loss)
+  for a, b in zip(grads, grads2[:-1]):
+    assert torch.equal(a, b)
+  # so the value gradient is the v_loss path alone: d/d baseline of
+  # mean((vs - baseline)^2) / 4 with vs held constant, and the policy's is
+  # the surrogate's and the entropy's with the advantages held constant
+  obs = losses_mod.normalize(data.observation.transpose(0, 1), normalizer)
+  baseline = losses_mod.mlp(value, obs).squeeze(-1)
+  v_only = torch.mean((seen['vs'] - baseline) ** 2) * 0.25
+  for a, b in zip(grads[len(policy) * 2:], torch.autograd.grad(v_only, params[len(policy) * 2:])):
+    torch.testing.assert_close(a, b, rtol=1e-12, atol=1e-15)
+
+
+# ---- ABI ------------------------------------------------------------------------------------
+
+def test_header_abi_and_exports():
+  src = open(os.path.join(ROOT, 'include', 'brax_amd.h')).read()
+  m = re.search(r'^int bx_compute_gae\s*\(([^;]*)\);', src, re.M)
+  assert m
+  names = [re.match(r'\s*(.*?)(\w+)\s*$', a).group(2) for a in m.group(1).replace('\n', ' ').split(',')]
+  assert names == [n for n, _ in abi.ARGS['bx_compute_gae']]
+  body = re.search(r'typedef struct bx_seq \{(.*?)\} bx_seq;', src, re.S).group(1)
+  assert re.findall(r'(\w+);', body) == [f for f, _ in abi.BxSeq._fields_]
+  assert 'bx_system' not in m.group(1)
+  assert 'bx_compute_gae' in _native.EXPORTS
+  assert abi.ABI_VERSION == 14 and '#define BX_ABI_VERSION 14' in src
+  lib = _native.lib()
+  assert lib.bx_abi_version() == 14
+  # null arguments fail with a message, no GPU touched
+  rc = lib.bx_compute_gae(1, 1, None, None, None, None, None, None, None, 1.0, 0.9, 0.95, None)
+  assert rc != 0 and b'null' in lib.bx_last_error()
+  # so do the size and stride checks, before any device call
+  buf = (C.c_float * 8)()
+  s = abi.BxSeq(C.addressof(buf), 2, 1)
+  zero_t, zero_e = abi.BxSeq(C.addressof(buf), 0, 1), abi.BxSeq(C.addressof(buf), 2, 0)
+  r = C.byref
+  call = lambda T, B, vs, adv, boot=C.addressof(buf): lib.bx_compute_gae(  # noqa: E731
+      T, B, r(s), r(s), r(s), r(s), boot, r(vs), r(adv), 1.0, 0.9, 0.95, None)
+  for args, word in (((0, 2, s, s), b'n_steps'), ((2, -1, s, s), b'n_envs'),
+                     ((2, 2, zero_t, s), b'stride'), ((2, 2, s, zero_e), b'stride'),
+                     ((2, 2, s, s, None), b'null')):
+    assert call(*args) != 0 and word in lib.bx_last_error(), (args[:2], lib.bx_last_error())
+  # an empty batch is a no-op, whatever the pointers
+  nul = abi.BxSeq(None, 0, 0)
+  assert lib.bx_compute_gae(3, 0, r(nul), r(nul), r(nul), r(nul), None, r(nul), r(nul), 1.0, 0.9,
+                            0.95, None) == 0
+
+
+# ---- train ----------------------------------------------------------------------------------
+
+def test_step_accounting_and_argument_checks():
+  a = ppo.step_accounting(num_timesteps=1920, num_evals=2, batch_size=32, unroll_length=5,
+                          num_minibatches=4, action_repeat=1, num_envs=64)
+  assert a.env_step_per_training_step == 32 * 5 * 4 * 1 == 640
+  assert (a.num_evals_after_init, a.num_training_steps_per_epoch, a.unrolls_per_training_step) == (1, 3, 2)
+  # the Ant notebook's configuration: 2048 x 32 sequences from 2048 envs
+  b = ppo.step_accounting(30_000_000, 10, 2048, 5, 32, 1, 2048)
+  assert b.env_step_per_training_step == 2048 * 5 * 32 and b.unrolls_per_training_step == 32
+  assert b.num_evals_after_init == 9
+  assert b.num_training_steps_per_epoch == math.ceil(30_000_000 / (9 * 327_680)) == 11
+  c = ppo.step_accounting(1000, 1, 8, 10, 2, 3, 4)  # num_evals 1: still one epoch
+  assert (c.env_step_per_training_step, c.num_evals_after_init, c.num_training_steps_per_epoch) == (480, 1, 3)
+  # the reference's assert, before any env or device is touched
+  with pytest.raises(AssertionError):
+    ppo.train('ant', num_timesteps=100, episode_length=10, num_envs=48, batch_size=32,
+              num_minibatches=4, device='cuda:0')
+  # the reference's argument names and defaults
+  import inspect
+  sig = inspect.signature(ppo.train).parameters
+  want = dict(action_repeat=1, num_envs=1, max_devices_per_host=None, num_eval_envs=128,
+              learning_rate=1e-4, entropy_cost=1e-4, discounting=0.9, seed=0, unroll_length=10,
+              batch_size=32, num_minibatches=16, num_updates_per_batch=2, num_evals=1,
+              normalize_observations=False, reward_scaling=1.0, clipping_epsilon=0.3,
+              gae_lambda=0.95, deterministic_eval=False, normalize_advantage=True, device=None)
+  for k, v in want.items():
+    assert sig[k].default == v, k
+  assert list(sig)[:3] == ['environment', 'num_timesteps', 'episode_length'] and 'progress_fn' in sig
+
+
+def test_networks_and_running_statistics():
+  policy, value = make_ppo_networks(7, 3)
+  assert [tuple(w.shape) for w, _ in policy] == [(7, 32), (32, 32), (32, 32), (32, 32), (32, 6)]
+  assert [tuple(w.shape) for w, _ in value] == [(7, 256)] + [(256, 256)] * 4 + [(256, 1)]
+  for w, b in policy + value:
+    assert w.requires_grad and b.requires_grad
+    w, b = w.detach(), b.detach()
+    assert float(b.abs().max()) == 0
+    lim = math.sqrt(3.0 / w.shape[0])  # lecun uniform
+    assert float(w.abs().max()) <= lim and float(w.abs().max()) > 0.8 * lim
+    assert abs(float(w.var()) - 1.0 / w.shape[0]) < 0.25 / w.shape[0]
+  # the normaliser: two batches against acme's update in float64
+  rng = np.random.default_rng(0)
+  rs = ppo.RunningStatistics(5, 'cpu')
+  mean, sv, count = np.zeros(5), np.zeros(5), 0.0
+  for shape in ((6, 4, 5), (3, 5)):
+    batch = rng.normal(size=shape) * 3 + 1
+    rs.update(torch.as_tensor(batch, dtype=torch.float32))
+    b = np.float32(batch).astype(np.float64).reshape(-1, 5)
+    count += len(b)
+    d_old = b - mean
+    mean = mean + d_old.sum(0) / count
+    sv = sv + (d_old * (b - mean)).sum(0)
+    std = np.clip(np.sqrt(np.maximum(sv, 0) / count), 1e-6, 1e6)
+    np.testing.assert_allclose(rs.mean, mean, rtol=1e-12)
+    np.testing.assert_allclose(rs.summed_variance, sv, rtol=1e-12)
+    np.testing.assert_allclose(rs.std, std, rtol=1e-12)
+    assert rs.count == count
+    assert torch.equal(rs.std_t, torch.as_tensor(std, dtype=torch.float32))
