@@ -1349,20 +1349,29 @@ static int check_draw(const bx_system* S, const bx_env_params* env, int64_t act_
   return 0;
 }
 
+// what an env launch has beyond the plain step, each entry point filling in
+// what it uses: on-device action draws, the policy action source, the
+// evaluation's sums, the population's extras, and the whole workgroup's
+// dynamic LDS where those kernels lay out words past the system's areas
+struct EnvLaunch {
+  const DrawSpec* draw = nullptr;
+  const PolArgs* pol = nullptr;
+  const EvalArgs* evl = nullptr;
+  const PopArgs* pop = nullptr;
+  size_t lds = 0;
+};
 static int env_step_impl(bx_system* S, const bx_env_params* env, int64_t n_envs,
                          const bx_env_state* in, const float* act, int64_t act_stride,
                          int64_t act_width, const bx_env_state* out, void* stream,
                          int32_t n_steps, int64_t act_step, int64_t out_step, int64_t rng_step,
-                         const DrawSpec* draw = nullptr, bool packed = false,
-                         const PolArgs* pol = nullptr, size_t pol_lds = 0,
-                         const EvalArgs* evl = nullptr, size_t evl_lds = 0,
-                         const PopArgs* pop = nullptr) {
+                         bool packed = false, const EnvLaunch& x = {}) {
+  const DrawSpec* draw = x.draw;
   if (!S || !env || !in || !out) return fail("null argument");
   DEVICE_SCOPE(S);
   if (check_env(S, env)) return 1;
   // an empty batch is a no-op (its buffers, the action included, may be null)
   if (n_envs <= 0) return n_envs == 0 ? 0 : fail("negative n_envs");
-  if ((draw || pol) ? check_draw(S, env, act_width) : check_act(S, act, act_stride, act_width)) return 1;
+  if ((draw || x.pol) ? check_draw(S, env, act_width) : check_act(S, act, act_stride, act_width)) return 1;
   if (!qp_ok(in->qp) || !qp_ok(out->qp)) return fail("null qp field");
   if (!in->done || !out->done || !out->reward || !out->obs) return fail("null env buffer");
   if (env->auto_reset && (!qp_ok(env->first_qp) || !env->first_obs))
@@ -1400,22 +1409,19 @@ static int env_step_impl(bx_system* S, const bx_env_params* env, int64_t n_envs,
     a.draw_hi = draw->hi;
     a.act_out = draw->act_out;
   }
-  const int fold = S->fold ? (1 | (S->jb ? 2 : 0) | (S->cb ? 4 : 0)) : 0;
-  if (pop)  // (evl_lds: the whole workgroup's, the population's words included)
-    HIP_OK(launch_env_eval_population(S->L, S->feat, S->gw, S->tpb, n_envs, evl_lds, as_stream(stream), a,
-                                      *pol, *evl, *pop, fold));
-  else if (evl && pol)  // (eval_plan admits SINGLE-mode systems only)
-    HIP_OK(launch_env_eval_policy(S->L, S->feat, S->gw, S->tpb, n_envs, evl_lds, as_stream(stream), a, *pol,
-                                  *evl, fold));
-  else if (evl)
-    HIP_OK(launch_env_eval_open(S->L, S->feat, S->gw, S->tpb, n_envs, evl_lds, as_stream(stream), a, *evl,
-                                fold));
-  else if (pol)  // (policy_plan admits SINGLE-mode systems only)
-    HIP_OK(launch_env_policy_single(S->L, S->feat, S->gw, S->tpb, n_envs, pol_lds, as_stream(stream), a,
-                                    *pol, S->fold ? (1 | (S->jb ? 2 : 0) | (S->cb ? 4 : 0)) : 0));
+  const int fold = fold_bits(S->fold, S->jb, S->cb);
+  hipStream_t s = as_stream(stream);
+  if (x.pop)  // (policy_plan and eval_plan admit SINGLE-mode systems only)
+    HIP_OK(launch_env_eval_population(S->L, S->feat, S->gw, S->tpb, n_envs, x.lds, s, a, *x.pol, *x.evl,
+                                      *x.pop, fold));
+  else if (x.evl && x.pol)
+    HIP_OK(launch_env_eval_policy(S->L, S->feat, S->gw, S->tpb, n_envs, x.lds, s, a, *x.pol, *x.evl, fold));
+  else if (x.evl)
+    HIP_OK(launch_env_eval_open(S->L, S->feat, S->gw, S->tpb, n_envs, x.lds, s, a, *x.evl, fold));
+  else if (x.pol)
+    HIP_OK(launch_env_policy_single(S->L, S->feat, S->gw, S->tpb, n_envs, x.lds, s, a, *x.pol, fold));
   else if (S->mode == 1)
-    HIP_OK(launch_env_step_single(S->L, S->feat, S->gw, S->tpb, n_envs, step_lds(S), as_stream(stream), a,
-                                  S->fold ? (1 | (S->jb ? 2 : 0) | (S->cb ? 4 : 0)) : 0));
+    HIP_OK(launch_env_step_single(S->L, S->feat, S->gw, S->tpb, n_envs, step_lds(S), s, a, fold));
   else if (S->mode == 3)  // MULTI-mode systems step envs with the item-loop kernel
     HIP_OK(launch_env_step_generic(S->L, 0, S->feat, S->tpb, n_envs,
                                    (size_t)S->hdr.env_words * 4, as_stream(stream), a));
@@ -1434,10 +1440,7 @@ static int env_step_packed(bx_system* S, const bx_env_params* env, int64_t n_env
                            const float* qp_in, const float* done_in, const float* steps_in,
                            const uint32_t* rng_in, const float* act, int64_t act_stride,
                            int64_t act_step, int64_t act_width, float* out, uint32_t* rng_out,
-                           void* stream, const DrawSpec* draw = nullptr,
-                           const PolArgs* pol = nullptr, size_t pol_lds = 0,
-                           const EvalArgs* evl = nullptr, size_t evl_lds = 0,
-                           const PopArgs* pop = nullptr) {
+                           void* stream, const EnvLaunch& x = {}) {
   if (!S || !env) return fail("null argument");
   if (n_envs <= 0) {
     if (check_env(S, env)) return 1;
@@ -1473,7 +1476,7 @@ static int env_step_packed(bx_system* S, const bx_env_params* env, int64_t n_env
   // one step's output block: qp | obs | reward, done, steps, truncation | metrics
   const int64_t block = B * (N * 16 + env->obs_size + 4 + env->n_metrics);
   return env_step_impl(S, env, n_envs, &in, act, act_stride, act_width, &o, stream, n_steps,
-                       act_step, block, B, draw, true, pol, pol_lds, evl, evl_lds, pop);
+                       act_step, block, B, true, x);
 }
 
 int bx_env_step_packed(bx_system* S, const bx_env_params* env, int64_t n_envs,
@@ -1506,8 +1509,10 @@ int bx_env_rollout_random(bx_system* S, const bx_env_params* env, int64_t n_envs
   if (check_env(S, env) || check_draw(S, env, act_width)) return 1;
   if (n_steps == 0) return 0;
   const DrawSpec d{seed, offset, step_stride, lo, hi, act_out};
+  EnvLaunch x;
+  x.draw = &d;
   return env_step_packed(S, env, n_envs, n_steps, qp_in, done_in, steps_in, rng_in, nullptr, 0, 0,
-                         act_width, out, rng_out, stream, &d);
+                         act_width, out, rng_out, stream, x);
 }
 
 // bx_env_rollout_policy's descriptor checked against its limits and laid out
@@ -1568,30 +1573,53 @@ static int policy_plan(const bx_system* S, const bx_env_params* env, const bx_po
   return 0;
 }
 
+// the policy entry points' shared prelude (bx_env_rollout_policy,
+// bx_env_eval_policy, bx_env_eval_population): their first checks in their
+// order, the plan into *q and *lds, and the launch's observation and noise
+// arguments. population: bx_env_eval_population's descriptor checks, which
+// come before the plans
+static int policy_prelude(const bx_system* S, const bx_env_params* env, int32_t n_steps,
+                          const bx_policy* policy, const float* obs_in, uint64_t seed,
+                          uint64_t offset, uint64_t step_stride, PolArgs* q, size_t* lds,
+                          bool population = false, const bx_population* pop = nullptr) {
+  if (!S || !env) return fail("null argument");
+  if (n_steps < 0) return fail("negative n_steps");
+  if (!policy) return fail("null policy");
+  if (population) {
+    if (!pop) return fail("null population");
+    if (pop->head != BX_HEAD_NORMAL_TANH && pop->head != BX_HEAD_IDENTITY)
+      return fail("population: unknown head");
+  }
+  const int64_t A = policy->action_size;
+  if (check_env(S, env) || check_draw(S, env, A) ||
+      policy_plan(S, env, policy, A, q, lds, population && pop->head == BX_HEAD_IDENTITY,
+                  population && pop->param_stride != 0))
+    return 1;
+  q->obs_in = obs_in;
+  q->seed = seed;
+  q->offset = offset;
+  q->step = step_stride;
+  return 0;
+}
+
 int bx_env_rollout_policy(bx_system* S, const bx_env_params* env, int64_t n_envs, int32_t n_steps,
                           const float* qp_in, const float* obs_in, const float* done_in,
                           const float* steps_in, const uint32_t* rng_in, const bx_policy* policy,
                           uint64_t seed, uint64_t offset, uint64_t step_stride, float* act_out,
                           float* raw_out, float* logp_out, float* out, uint32_t* rng_out,
                           void* stream) {
-  if (!S || !env) return fail("null argument");
-  if (n_steps < 0) return fail("negative n_steps");
-  if (!policy) return fail("null policy");
-  const int64_t A = policy->action_size;
   PolArgs q{};
-  size_t lds = 0;
-  if (check_env(S, env) || check_draw(S, env, A) || policy_plan(S, env, policy, A, &q, &lds)) return 1;
+  EnvLaunch x;
+  if (policy_prelude(S, env, n_steps, policy, obs_in, seed, offset, step_stride, &q, &x.lds)) return 1;
   if (n_steps == 0) return 0;
   if (n_envs > 0 && !obs_in) return fail("null obs_in");
-  q.obs_in = obs_in;
   q.raw_out = raw_out;
   q.logp_out = logp_out;
-  q.seed = seed;
-  q.offset = offset;
-  q.step = step_stride;
   const DrawSpec d{0, 0, 0, 0.f, 0.f, act_out};
+  x.draw = &d;
+  x.pol = &q;
   return env_step_packed(S, env, n_envs, n_steps, qp_in, done_in, steps_in, rng_in, nullptr, 0, 0,
-                         A, out, rng_out, stream, &d, &q, lds);
+                         policy->action_size, out, rng_out, stream, x);
 }
 
 // the evaluation kernels' on-chip words laid out past `base` bytes of the
@@ -1613,28 +1641,24 @@ int bx_env_eval_policy(bx_system* S, const bx_env_params* env, int64_t n_envs, i
                        const float* steps_in, const uint32_t* rng_in, const bx_policy* policy,
                        uint64_t seed, uint64_t offset, uint64_t step_stride, const float* eval_in,
                        float* out, float* eval_out, uint32_t* rng_out, void* stream) {
-  if (!S || !env) return fail("null argument");
-  if (n_steps < 0) return fail("negative n_steps");
-  if (!policy) return fail("null policy");
-  const int64_t A = policy->action_size;
   PolArgs q{};
   EvalArgs v{};
-  size_t pol_lds = 0, lds = 0;
-  if (check_env(S, env) || check_draw(S, env, A) || policy_plan(S, env, policy, A, &q, &pol_lds) ||
-      eval_plan(S, env, pol_lds, &v, &lds))
+  EnvLaunch x;
+  size_t pol_lds = 0;
+  if (policy_prelude(S, env, n_steps, policy, obs_in, seed, offset, step_stride, &q, &pol_lds) ||
+      eval_plan(S, env, pol_lds, &v, &x.lds))
     return 1;
   if (n_steps == 0) return 0;
   if (n_envs > 0 && !obs_in) return fail("null obs_in");
   if (n_envs > 0 && !eval_out) return fail("null eval_out");
-  q.obs_in = obs_in;
-  q.seed = seed;
-  q.offset = offset;
-  q.step = step_stride;
   v.in = eval_in;
   v.out = eval_out;
   const DrawSpec d{0, 0, 0, 0.f, 0.f, nullptr};
+  x.draw = &d;
+  x.pol = &q;
+  x.evl = &v;
   return env_step_packed(S, env, n_envs, n_steps, qp_in, done_in, steps_in, rng_in, nullptr, 0, 0,
-                         A, out, rng_out, stream, &d, &q, pol_lds, &v, lds);
+                         policy->action_size, out, rng_out, stream, x);
 }
 
 int bx_env_eval_population(bx_system* S, const bx_env_params* env, int64_t n_envs, int32_t n_steps,
@@ -1643,22 +1667,14 @@ int bx_env_eval_population(bx_system* S, const bx_env_params* env, int64_t n_env
                            uint64_t seed, uint64_t offset, uint64_t step_stride,
                            const float* eval_in, float* out, float* eval_out, uint32_t* rng_out,
                            bx_population* pop, void* stream) {
-  if (!S || !env) return fail("null argument");
-  if (n_steps < 0) return fail("negative n_steps");
-  if (!policy) return fail("null policy");
-  if (!pop) return fail("null population");
-  if (pop->head != BX_HEAD_NORMAL_TANH && pop->head != BX_HEAD_IDENTITY)
-    return fail("population: unknown head");
-  const int64_t A = policy->action_size;
-  const int64_t stride = pop->param_stride;
   PolArgs q{};
   EvalArgs v{};
   PopArgs n{};
   size_t pol_lds = 0, ev_lds = 0;
-  if (check_env(S, env) || check_draw(S, env, A) ||
-      policy_plan(S, env, policy, A, &q, &pol_lds, pop->head == BX_HEAD_IDENTITY, stride != 0) ||
+  if (policy_prelude(S, env, n_steps, policy, obs_in, seed, offset, step_stride, &q, &pol_lds, true, pop) ||
       eval_plan(S, env, pol_lds, &v, &ev_lds))
     return 1;
+  const int64_t stride = pop->param_stride;
   if (stride != 0 && (stride < q.n_params || (stride & 3)))
     return fail("population: param_stride must be 0 or a multiple of 4 floats no smaller than n_params (" +
                 std::to_string(q.n_params) + ")");
@@ -1680,10 +1696,6 @@ int bx_env_eval_population(bx_system* S, const bx_env_params* env, int64_t n_env
   if (n_steps == 0) return 0;
   if (n_envs > 0 && !obs_in) return fail("null obs_in");
   if (n_envs > 0 && !eval_out) return fail("null eval_out");
-  q.obs_in = obs_in;
-  q.seed = seed;
-  q.offset = offset;
-  q.step = step_stride;
   if (pop->head == BX_HEAD_IDENTITY) q.det = 1;  // (no noise is drawn; the head returns before reading it)
   v.in = eval_in;
   v.out = eval_out;
@@ -1693,8 +1705,14 @@ int bx_env_eval_population(bx_system* S, const bx_env_params* env, int64_t n_env
   n.head = pop->head;
   n.reward_shift = pop->reward_shift;
   const DrawSpec d{0, 0, 0, 0.f, 0.f, nullptr};
+  EnvLaunch x;
+  x.draw = &d;
+  x.pol = &q;
+  x.evl = &v;
+  x.pop = &n;
+  x.lds = lds;  // (the whole workgroup's, the population's words included)
   return env_step_packed(S, env, n_envs, n_steps, qp_in, done_in, steps_in, rng_in, nullptr, 0, 0,
-                         A, out, rng_out, stream, &d, &q, pol_lds, &v, lds, &n);
+                         policy->action_size, out, rng_out, stream, x);
 }
 
 int bx_env_eval_packed(bx_system* S, const bx_env_params* env, int64_t n_envs, int32_t n_steps,
@@ -1705,16 +1723,16 @@ int bx_env_eval_packed(bx_system* S, const bx_env_params* env, int64_t n_envs, i
   if (!S || !env) return fail("null argument");
   if (n_steps < 0) return fail("negative n_steps");
   EvalArgs v{};
-  size_t lds = 0;
-  if (check_env(S, env) || eval_plan(S, env, step_lds(S), &v, &lds)) return 1;
+  EnvLaunch x;
+  if (check_env(S, env) || eval_plan(S, env, step_lds(S), &v, &x.lds)) return 1;
   if (n_steps == 0) return 0;
   if (act_step_stride < 0) return fail("negative action step stride");
   if (n_envs > 0 && !eval_out) return fail("null eval_out");
   v.in = eval_in;
   v.out = eval_out;
+  x.evl = &v;
   return env_step_packed(S, env, n_envs, n_steps, qp_in, done_in, steps_in, rng_in, act,
-                         act_stride, act_step_stride, act_width, out, rng_out, stream, nullptr,
-                         nullptr, 0, &v, lds);
+                         act_stride, act_step_stride, act_width, out, rng_out, stream, x);
 }
 
 int bx_system_info(bx_system* S, int64_t n_envs, const bx_qp* qp, const bx_info* info, void* stream) {

@@ -1,10 +1,12 @@
-// pbd_launch.h — host-side launch entry points of pbd_single.hip,
-// pbd_generic.hip and phase_kernels.hip
+// pbd_launch.h — host-side launch entry points of the step kernels' units and
+// phase_kernels.hip, and the one launcher of the env launch units
+// (launch_env_family over the decisions of pbd_dispatch.h)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/brax_amd.h"
+#include "pbd_dispatch.h"
 #include "pbd_layout.h"
 
 namespace bx {
@@ -133,37 +135,103 @@ struct ResetArgs {
 };
 
 // one kernel launch (the translation units' launchers)
-template <typename Args>
-static void launch_one(void (*k)(Args), dim3 grid, int tpb, size_t lds, hipStream_t s, const Args& a) {
+template <typename... Args>
+static void launch_one(void (*k)(Args...), dim3 grid, int tpb, size_t lds, hipStream_t s, const Args&... a) {
   // tpb threads per workgroup (a multiple of L, <= 64): 64 / L envs share a
   // wavefront by default; 32 halves that (twice the waves for one batch)
   if (lds > 65536) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, grid, dim3(tpb), lds, s, a);
+  hipLaunchKernelGGL(k, grid, dim3(tpb), lds, s, a...);
 }
+// the SINGLE-mode grid: tpb / L envs per workgroup
+inline dim3 single_grid(int L, int tpb, int64_t n_envs) {
+  const int epb = tpb / L;
+  return dim3((unsigned)((n_envs + epb - 1) / epb));
+}
+// compute units of the current device (the launch runs under the system's
+// device scope), cached per device
+inline int cu_count() {
+  static int cached[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (!cached[dev]) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cached[dev] = n;
+  }
+  return cached[dev];
+}
+
+// One env launch of a unit's kernel family Fam: the env kind's own kernel
+// where kind_variant (pbd_dispatch.h) grants one, Ant's wide twin past one
+// wave per SIMD, else the variant list's (single_variant yields listed
+// variants only, so its default arm is not reached). Both switches are
+// generated from the lists, so nothing is selected without being
+// instantiated, and a family instantiates no kind kernel it does not have.
+// Fam states what differs between the units: `id` (its EnvFamily) and
+//   template <int L, int F, int M, int EK> static auto kernel(const EnvArgs&, bool wide)
+// the instantiation's kernel for this launch; x: its kernels' arguments
+// after EnvArgs
+#define BX_KIND_CASE(VF, VM, VEK, UNUSED)                                                     \
+  case kind_key(VF, VM, VEK):                                                                 \
+    if constexpr (family_has(Fam::id, VEK)) {                                                 \
+      const bool wide = VEK == EK_ANT && ant_wide(grid.x, tpb, cu_count());                   \
+      launch_one(Fam::template kernel<16, VF, VM, VEK>(a, wide), grid, tpb, lds, s, a, x...); \
+      return hipGetLastError();                                                               \
+    }                                                                                         \
+    break;
+#define BX_VARIANT_CASE(VL, VF, VM, UNUSED)                                                 \
+  case single_key(VL, VF, VM):                                                              \
+    launch_one(Fam::template kernel<VL, VF, VM, EK_ANY>(a, false), grid, tpb, lds, s, a, x...); \
+    break;
+template <class Fam, typename... Extra>
+static hipError_t launch_env_family(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
+                                    hipStream_t s, int fold, const EnvArgs& a, const Extra&... x) {
+  const dim3 grid = single_grid(L, tpb, n_envs);
+  const KindVariant k = kind_variant(Fam::id, L, feat, gw, a.P.kind, fold);
+  switch (kind_key(k.F, k.M, k.EK)) {
+    BX_KIND_VARIANTS(BX_KIND_CASE, 0)
+    default: break;
+  }
+  const SingleVariant v = single_variant(L, feat, gw);
+  switch (single_key(v.L, v.F, v.M)) {
+    BX_SINGLE_VARIANTS(BX_VARIANT_CASE, 0)
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+// the family of a rollout kernel template and its wide twin
+#define BX_ENV_FAMILY(NAME, ID, KERNEL, WIDE_KERNEL)                 \
+  struct NAME {                                                      \
+    static constexpr EnvFamily id = ID;                              \
+    template <int L, int F, int M, int EK>                           \
+    static auto kernel(const EnvArgs&, bool wide) {                  \
+      if constexpr (EK == EK_ANT)                                    \
+        if (wide) return &WIDE_KERNEL<L, 1, F, M, EK>;               \
+      return &KERNEL<L, 1, F, M, EK>;                                \
+    }                                                                \
+  };
 
 // SINGLE-mode step kernels (fast-reciprocal translation unit)
 hipError_t launch_system_step_single(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
                                      hipStream_t s, const StepArgs& a);
+// the env launch units (SINGLE mode only), launch_env_family each; fold: the
+// plan's fold_bits. Steps and open-loop K-step rollouts (pbd_single.hip)
 hipError_t launch_env_step_single(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
                                   hipStream_t s, const EnvArgs& a, int fold);
-// the K-step rollout with the policy action source (pbd_policy.hip; SINGLE
-// mode only); policy_lds_budget: the largest per-workgroup LDS at which the
-// launch still stages the parameters
+// the K-step rollout with the policy action source (pbd_policy.hip)
 hipError_t launch_env_policy_single(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
                                     hipStream_t s, const EnvArgs& a, const PolArgs& q, int fold);
 hipError_t launch_normal_slabs(float* out, int64_t slab_n, int64_t n_slabs, uint64_t seed,
                                uint64_t offset, uint64_t slab_stride, const int64_t* epoch,
                                uint64_t epoch_stride, hipStream_t s);
-// whole evaluations (env_step_body's EVL; SINGLE mode only): the policy form
-// (pbd_eval.hip, launch_env_policy_single's selection) and the open-loop form
-// (pbd_eval_open.hip, launch_env_step_single's selection for a K-step launch)
+// whole evaluations (env_step_body's EVL): the policy form (pbd_eval.hip) and
+// the open-loop form (pbd_eval_open.hip)
 hipError_t launch_env_eval_policy(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
                                   hipStream_t s, const EnvArgs& a, const PolArgs& q,
                                   const EvalArgs& v, int fold);
 hipError_t launch_env_eval_open(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
                                 hipStream_t s, const EnvArgs& a, const EvalArgs& v, int fold);
-// one episode per perturbed policy (env_step_body's POP; pbd_pop.hip,
-// launch_env_policy_single's selection)
+// one episode per perturbed policy (env_step_body's POP; pbd_pop.hip)
 hipError_t launch_env_eval_population(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,
                                       hipStream_t s, const EnvArgs& a, const PolArgs& q,
                                       const EvalArgs& v, const PopArgs& n, int fold);
