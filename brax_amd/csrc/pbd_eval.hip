@@ -20,11 +20,12 @@ __global__ void __launch_bounds__(L > 64 ? L : 64) BX_STEP_ATTR
 env_eval_policy_kernel(EnvArgs A, PolArgs Q, EvalArgs V) {
   env_step_body<L, MODE, F, M, EK, true, false, true, true>(A, Q, V);
 }
-// the Ant kernel held to 256 registers, as env_policy_rollout_wide_kernel
+// the Ant kernel held to 256 registers, as env_policy_rollout_wide_kernel (ZH
+// off: with the frozen side in registers it spilled 6 VGPRs, 28 B of scratch)
 template <int L, int MODE, int F, int M, int EK = EK_ANY>
 __global__ void __launch_bounds__(L > 64 ? L : 64) __attribute__((amdgpu_waves_per_eu(2)))
 env_eval_policy_wide_kernel(EnvArgs A, PolArgs Q, EvalArgs V) {
-  env_step_body<L, MODE, F, M, EK, true, false, true, true>(A, Q, V);
+  env_step_body<L, MODE, F, M, EK, true, false, true, true, false, false>(A, Q, V);
 }
 
 BX_ENV_FAMILY(EvalPolicyFamily, FAM_EVAL_POLICY, env_eval_policy_kernel, env_eval_policy_wide_kernel)

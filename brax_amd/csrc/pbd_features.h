@@ -59,6 +59,19 @@ constexpr bool cb_feat(int F) {
 #endif
 }
 
+// CBH (the CB kernels): the frozen plane side of the lane's row (its pose and
+// the plane normal rotate((0, 0, 1), rot)) read from LDS once per launch and
+// after an AutoReset instead of in every collision pass, and the frozen
+// bodies' records written once per launch instead of every step.
+// A/B switch -DBX_NO_CBH: the CB passes with their per-pass loads.
+constexpr bool cbh_feat(int F) {
+#if defined(BX_NO_CBH)
+  return false;
+#else
+  return cb_feat(F);
+#endif
+}
+
 #if defined(__HIPCC__)
 template <int F, int M> __device__ __forceinline__ constexpr int cl_width() {
   return (F & F_C16) ? 16 : M;

@@ -664,6 +664,18 @@ __device__ __forceinline__ void contact_gen(const RowC& R, const QP& a, const QP
   vel = (a.vel + cross(a.ang, pos - a.pos)) - (b.vel + cross(b.ang, pos - b.pos));
 }
 
+// contact_gen's capsule-plane arm on a plane body whose normal nb =
+// rotate((0, 0, 1), b.rot) the caller holds (CBH: a frozen body's, formed once)
+__device__ __forceinline__ void contact_gen_plane(const RowC& R, const QP& a, v3 bpos, v3 nb,
+                                                  v3& pos, v3& vel, v3& n, float& pen) {
+  BX_IEEE_IN_CONTACT
+  v3 e = a.pos + rotate(R.a_end, a.rot);
+  n = nb;
+  pos = e - n * R.a_rad;
+  vel = a.vel + cross(a.ang, pos - a.pos);
+  pen = dot(bpos - pos, n);
+}
+
 // ---- extended contact functions (item-loop kernels only) -----------------
 
 __device__ __forceinline__ float pdiv(float a, float b) { return (float)((double)a / (double)b); }
@@ -2736,6 +2748,34 @@ __device__ __forceinline__ void own_contact(v3 v, q4 q, float f, float eps, v3& 
   r = q4{r0.w / d0, r0.x / d0, r0.y / d0, r0.z / d0};
 }
 
+// CBH: the frozen b body of a CB lane's row, in registers. A frozen body's
+// record changes only where the caller's state or AutoReset's first_qp is
+// copied in, so it is read where that happens, not in every collision pass:
+// its record, and the plane normal contact_gen forms from it (the same rotate
+// call on the same words)
+struct FrozenB {
+  QP b;
+  v3 n;
+};
+__device__ __forceinline__ FrozenB load_frozen(const float* rec) {
+  FrozenB Z;
+  Z.b = ldqp(rec);
+  Z.n = rotate(mk(0.f, 0.f, 1.f), Z.b.rot);
+  return Z;
+}
+// CBH: the records of the bodies on no joint side that something reads
+// outside the step (the observation's contact sums: exact zeros, as the JB
+// prologue leaves them every step), once per launch; their prev / rb records
+// have no reader (the CB rows are one-way: neither pass takes the b side's)
+__device__ __forceinline__ void init_frozen_records(const BlobHdr& H, const Env& E, int lane) {
+  if (lane < H.N) {
+    float* acc = E.acc + lane * ACC_STRIDE;
+    st3(acc + ACC_ICV, mk(0.f, 0.f, 0.f));
+    st3(acc + ACC_ICA, mk(0.f, 0.f, 0.f));
+    st3(acc + ACC_IAA, mk(0.f, 0.f, 0.f));
+  }
+}
+
 // Euler.velocity_projection (integrators.py:122-146) on one body
 __device__ __forceinline__ void vproj(QP& q, v3 ppos, q4 prot, const BodyC& B, float h,
                                       bool bare = false, bool fast = false) {
@@ -2766,11 +2806,17 @@ __device__ __forceinline__ void vproj(QP& q, v3 ppos, q4 prot, const BodyC& B, f
 // tests compile-time true. (Tried for the Ant kernel, 16 lanes = 8 joints x 2
 // sides: 190 fewer SALU per step, no faster — a wave's SALU issue hides
 // behind its VALU — and the merged blocks contract differently; unused.)
-template <int L, int F, int M, bool FOLD = false, bool NOINFO = false, bool FULL = false>
+// CBH (the CB kernels, pbd_features.h cbh_feat): Z holds the frozen b body of
+// the lane's row as the caller read it (load_frozen: once per launch and
+// after an AutoReset), so the contact passes read nothing of it from LDS, and
+// the frozen bodies' records are the caller's (init_frozen_records)
+template <int L, int F, int M, bool FOLD = false, bool NOINFO = false, bool FULL = false,
+          bool CBH = false>
 __device__ void pbd_step_single(const Cst& c, const BlobHdr& H, const Env& E, int lane, bool valid,
                                 const float* act, int aw, const Hoist<M, cl_width<F, M>()>& X,
-                                v3& icv, v3& ica, v3& iaa) {
+                                v3& icv, v3& ica, v3& iaa, const FrozenB Z = FrozenB{}) {
   static_assert(!FULL || ((F & F_JH) != 0 && L == 16), "FULL: the 16-lane joint halves");
+  static_assert(!CBH || (FOLD && (F & F_JH) != 0 && (F & F_C16) == 0 && cb_feat(F)), "CBH: a CB kernel");
   const bool hasB = FULL || X.hasB, hasJ = FULL || X.hasJ, hasA = FULL || X.hasA;
 #ifdef BX_STAMPS
   unsigned long long st_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -2823,7 +2869,8 @@ __device__ void pbd_step_single(const Cst& c, const BlobHdr& H, const Env& E, in
     // one-way rows only: checked on the host) as their own lanes would leave
     // them: the previous-substep slot at their (unchanging) pose, zero contact
     // sums; the side bodies' copies overwrite their own records below
-    if (lane < H.N) {
+    // (CBH: the caller's init_frozen_records, once per launch)
+    if (!CBH && lane < H.N) {
       const float* r = E.qp + lane * QP_STRIDE;
       const QP o = ldqp(r);
       st_slot(E.prev + lane * PREV_STRIDE, o.pos, o.rot, 0.f);
@@ -2998,20 +3045,30 @@ __device__ void pbd_step_single(const Cst& c, const BlobHdr& H, const Env& E, in
       // The four stretches of the passes below, each on the body's lane: the
       // row's a body is the lane's q, its previous-substep pose ppos / prot,
       // its slot and row data stay in registers; the b body is frozen (its
-      // records: the prologue's). A lane whose body has no row runs the same
-      // instructions on row 0's constants and takes the zero slot's sums.
+      // records: the prologue's; CBH: the caller's copy Z, no LDS read). A
+      // lane whose body has no row runs the same instructions on row 0's constants and takes the zero slot's sums.
       // `held` stands where a value went through LDS, so each stretch
       // contracts its products as it did between its loads and stores
       const RowC& R = X.R;
       v3 oap = z3, oav = z3, oaa = z3, rop = z3, rov = z3, roa = z3;
       q4 oar = z4;
       if (hasB) {
-        const QP b = ldqp(E.qp + R.b * QP_STRIDE);
+        QP b;
         v3 pbp, obp, cvel;
         q4 pbr, obr;
-        float unused;
-        ld_slot(E.prev + R.b * PREV_STRIDE, pbp, pbr, unused);
-        contact_gen<F>(R, q, b, cpos, cvel, cn, pen);
+        if constexpr (CBH) {
+          // the frozen side as the caller read it (opaque since: load_frozen's
+          // caller holds it); its previous-substep slot is its pose
+          b = Z.b;
+          pbp = b.pos;
+          pbr = b.rot;
+          contact_gen_plane(R, q, b.pos, Z.n, cpos, cvel, cn, pen);
+        } else {
+          b = ldqp(E.qp + R.b * QP_STRIDE);
+          float unused;
+          ld_slot(E.prev + R.b * PREV_STRIDE, pbp, pbr, unused);
+          contact_gen<F>(R, q, b, cpos, cvel, cn, pen);
+        }
         dl = position_contact<F>(R, q, b, ppos, prot, pbp, pbr, cpos, cn, pen, oap, oar, obp, obr);
         if (!X.hasR) {
           oap = z3;
@@ -3039,9 +3096,18 @@ __device__ void pbd_step_single(const Cst& c, const BlobHdr& H, const Env& E, in
       }
       BX_STAMP(5);
       if (hasB) {
-        const QP b = ldqp(E.qp + R.b * QP_STRIDE);
+        QP b;
         v3 rbp, rbv, rba, obv, oba;
-        ld_rb(E.rb + R.b * RB_STRIDE, rbp, rbv, rba);
+        if constexpr (CBH) {
+          // (its qp_right_before record: its pos, vel, ang)
+          b = Z.b;
+          rbp = b.pos;
+          rbv = b.vel;
+          rba = b.ang;
+        } else {
+          b = ldqp(E.qp + R.b * QP_STRIDE);
+          ld_rb(E.rb + R.b * RB_STRIDE, rbp, rbv, rba);
+        }
         velocity_contact<F>(R, h, q, b, rop, rov, roa, rbp, rbv, rba, cpos, cn, pen, dl, oav, oaa,
                             obv, oba);
         if (!X.hasR) {
@@ -4753,8 +4819,12 @@ __device__ __forceinline__ float* policy_eval(const PolArgs& Q, const float* W, 
 // from N.mom_in before step 0, updated before each step's policy evaluation
 // with the env's active flag as the weight, stored to N.mom_out by the last
 // step (null: no moments, no words)
+// ZH (the CB kernels, pbd_features.h cbh_feat): the frozen side of each
+// lane's contact row stays in registers over the launch (FrozenB), read
+// after the state is in LDS and again after a step in which the lane's env
+// took AutoReset's first_qp
 template <int L, int MODE, int F, int M, int EK = EK_ANY, bool PK = false, bool ONE = false,
-          bool POL = false, bool EVL = false, bool POP = false>
+          bool POL = false, bool EVL = false, bool POP = false, bool ZH = true>
 __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q = PolArgs{},
                                               const EvalArgs& V = EvalArgs{},
                                               const PopArgs& N = PopArgs{}) {
@@ -4935,6 +5005,23 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
     }
   }
   BX_PSTAMP(8);
+  // CBH: the frozen b body of the lane's row from the record just stored
+  // (any start state: nothing of it is assumed), opaque from here on as a
+  // value out of LDS is, and the frozen bodies' zero contact sums
+  constexpr bool CBH = ZH && JBK && cbh_feat(F);
+  FrozenB Z{};
+  auto freeze = [&]() {
+    if (X.hasB) {
+      Z = load_frozen(E.qp + X.R.b * QP_STRIDE);
+      held(Z.b.pos); held(Z.b.rot); held(Z.b.vel); held(Z.b.ang);
+      held(Z.n);
+    }
+  };
+  if constexpr (CBH) {
+    esync<L>();
+    init_frozen_records(H, E, lane);
+    freeze();
+  }
   const int nst = ONE ? 1 : (A.n_steps > 1 ? A.n_steps : 1);
   for (int t = 0; t < nst; t++) {
   // whether this step stores its outputs (EVL: the last one only)
@@ -5140,7 +5227,8 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
     esync<L>();
     if constexpr (S) {
       v3 ica, iaa;
-      pbd_step_single<L, F, M, EK != EK_ANY, true>(c, H, E, lane, valid, sact, saw, X, icv, ica, iaa);
+      pbd_step_single<L, F, M, EK != EK_ANY, true, false, CBH>(c, H, E, lane, valid, sact, saw, X, icv,
+                                                               ica, iaa, Z);
     } else if (H.spring) {
       spring_step<L, F>(c, H, E, lane, valid, sact, saw);
     } else {
@@ -5440,6 +5528,10 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   steps_in = steps;
   rng_c += (uint32_t)reps;
   esync<L>();
+  if constexpr (CBH) {
+    // the env's records are first_qp's now, its frozen bodies' among them
+    if (valid && reset_now && t + 1 < nst) freeze();
+  }
   }  // steps
   BX_KSTAMP(14);
 }

@@ -19,11 +19,12 @@ __global__ void __launch_bounds__(L > 64 ? L : 64) BX_STEP_ATTR
 env_policy_rollout_kernel(EnvArgs A, PolArgs Q) {
   env_step_body<L, MODE, F, M, EK, true, false, true>(A, Q);
 }
-// the Ant kernel held to 256 registers, as env_rollout_wide_kernel
+// the Ant kernel held to 256 registers, as env_rollout_wide_kernel (ZH off:
+// with the frozen side in registers it spilled 5 VGPRs, 24 B of scratch)
 template <int L, int MODE, int F, int M, int EK = EK_ANY>
 __global__ void __launch_bounds__(L > 64 ? L : 64) __attribute__((amdgpu_waves_per_eu(2)))
 env_policy_rollout_wide_kernel(EnvArgs A, PolArgs Q) {
-  env_step_body<L, MODE, F, M, EK, true, false, true>(A, Q);
+  env_step_body<L, MODE, F, M, EK, true, false, true, false, false, false>(A, Q);
 }
 
 BX_ENV_FAMILY(PolicyFamily, FAM_POLICY, env_policy_rollout_kernel, env_policy_rollout_wide_kernel)

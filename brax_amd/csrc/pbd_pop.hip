@@ -20,11 +20,12 @@ __global__ void __launch_bounds__(L > 64 ? L : 64) BX_STEP_ATTR
 env_eval_pop_kernel(EnvArgs A, PolArgs Q, EvalArgs V, PopArgs N) {
   env_step_body<L, MODE, F, M, EK, true, false, true, true, true>(A, Q, V, N);
 }
-// the Ant kernel held to 256 registers, as env_eval_policy_wide_kernel
+// the Ant kernel held to 256 registers, as env_eval_policy_wide_kernel (ZH
+// off: with the frozen side in registers its scratch grew from 52 to 88 B)
 template <int L, int MODE, int F, int M, int EK = EK_ANY>
 __global__ void __launch_bounds__(L > 64 ? L : 64) __attribute__((amdgpu_waves_per_eu(2)))
 env_eval_pop_wide_kernel(EnvArgs A, PolArgs Q, EvalArgs V, PopArgs N) {
-  env_step_body<L, MODE, F, M, EK, true, false, true, true, true>(A, Q, V, N);
+  env_step_body<L, MODE, F, M, EK, true, false, true, true, true, false>(A, Q, V, N);
 }
 
 BX_ENV_FAMILY(PopulationFamily, FAM_POPULATION, env_eval_pop_kernel, env_eval_pop_wide_kernel)
