@@ -93,6 +93,8 @@ _SIGS = {
     'bx_env_eval_packed': abi.SIGNATURES['bx_env_eval_packed'],
     'bx_env_eval_population': abi.SIGNATURES['bx_env_eval_population'],
     'bx_compute_gae': abi.SIGNATURES['bx_compute_gae'],
+    'bx_population_perturb': abi.SIGNATURES['bx_population_perturb'],
+    'bx_population_delta': abi.SIGNATURES['bx_population_delta'],
 }
 
 EXPORTS = tuple(_SIGS)

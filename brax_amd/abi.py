@@ -153,8 +153,19 @@ COMPUTE_GAE_ARGS = (
     ('truncation', _seq), ('values', _seq), ('bootstrap', _vp), ('vs', _seq),
     ('advantages', _seq), ('reward_scaling', C.c_float), ('discount', C.c_float),
     ('lambda', C.c_float), ('stream', _vp))
+POPULATION_DELTA_CHUNK = 64  # BX_POPULATION_DELTA_CHUNK
+POPULATION_PERTURB_ARGS = (
+    ('rows', _vp), ('theta', _vp), ('n_directions', C.c_int64), ('n_params', C.c_int64),
+    ('stride', C.c_int64), ('sigma', C.c_double), ('seed', C.c_uint64), ('offset', C.c_uint64),
+    ('antithetic', C.c_int), ('frozen', _vp), ('stream', _vp))
+POPULATION_DELTA_ARGS = (
+    ('out', _vp), ('weights', _vp), ('n_directions', C.c_int64), ('n_params', C.c_int64),
+    ('seed', C.c_uint64), ('offset', C.c_uint64), ('frozen', _vp), ('workspace', _vp),
+    ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
 ARGS = {'bx_env_eval_policy': EVAL_POLICY_ARGS, 'bx_env_eval_packed': EVAL_PACKED_ARGS,
-        'bx_env_eval_population': EVAL_POPULATION_ARGS, 'bx_compute_gae': COMPUTE_GAE_ARGS}
+        'bx_env_eval_population': EVAL_POPULATION_ARGS, 'bx_compute_gae': COMPUTE_GAE_ARGS,
+        'bx_population_perturb': POPULATION_PERTURB_ARGS,
+        'bx_population_delta': POPULATION_DELTA_ARGS}
 SIGNATURES = {name: ([t for _, t in args], C.c_int) for name, args in ARGS.items()}
 
 

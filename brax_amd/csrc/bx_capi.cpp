@@ -2013,4 +2013,58 @@ int bx_compute_gae(int64_t n_steps, int64_t n_envs, const bx_seq* reward, const 
   return 0;
 }
 
+int bx_population_perturb(float* rows, const float* theta, int64_t n_directions, int64_t n_params,
+                          int64_t stride, double sigma, uint64_t seed, uint64_t offset,
+                          int antithetic, const uint8_t* frozen, void* stream) {
+  if (!rows || !theta) return fail("null argument");
+  if (n_directions < 1) return fail("n_directions must be >= 1");
+  if (n_params < 1) return fail("n_params must be >= 1");
+  if (stride < n_params) return fail("stride below n_params");
+  if (n_params > ((int64_t)1 << 40) / n_directions) return fail("too many samples for one launch");
+  if (stride > ((int64_t)1 << 41) / n_directions) return fail("stride too large");
+  const int64_t members = antithetic ? 2 * n_directions : n_directions;
+  const uintptr_t r0 = (uintptr_t)rows, r1 = r0 + (size_t)((members - 1) * stride + n_params) * 4;
+  const uintptr_t t0 = (uintptr_t)theta, t1 = t0 + (size_t)n_params * 4;
+  if (r0 < t1 && t0 < r1) return fail("rows overlap theta");
+  int dev = -1;
+  hipStream_t st = as_stream(stream);
+  if (st) HIP_OK(hipStreamGetDevice(st, &dev));
+  else HIP_OK(hipGetDevice(&dev));
+  DeviceScope scope(dev);
+  if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
+  HIP_OK(launch_population_perturb(rows, theta, frozen, n_directions, n_params, stride, sigma, seed,
+                                   offset, antithetic ? 1 : 0, st));
+  return 0;
+}
+
+int bx_population_delta(float* out, const float* weights, int64_t n_directions, int64_t n_params,
+                        uint64_t seed, uint64_t offset, const uint8_t* frozen, void* workspace,
+                        int64_t* workspace_bytes, void* stream) {
+  if (!workspace_bytes) return fail("null argument");
+  if (n_directions < 1) return fail("n_directions must be >= 1");
+  if (n_params < 1) return fail("n_params must be >= 1");
+  if (n_params > ((int64_t)1 << 40) / n_directions) return fail("too many samples for one launch");
+  const int64_t chunks = (n_directions + BX_POPULATION_DELTA_CHUNK - 1) / BX_POPULATION_DELTA_CHUNK;
+  const int64_t need = chunks * n_params * (int64_t)sizeof(double);
+  if (!workspace) {  // the size query
+    *workspace_bytes = need;
+    return 0;
+  }
+  if (!out || !weights) return fail("null argument");
+  if (*workspace_bytes < need)
+    return fail("workspace of " + std::to_string(*workspace_bytes) + " bytes, " +
+                std::to_string(need) + " needed");
+  if ((uintptr_t)workspace & 7) return fail("workspace not 8-byte aligned");
+  if (chunks > 65535) return fail("too many directions for one launch");
+  int dev = -1;
+  hipStream_t st = as_stream(stream);
+  if (st) HIP_OK(hipStreamGetDevice(st, &dev));
+  else HIP_OK(hipGetDevice(&dev));
+  DeviceScope scope(dev);
+  if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
+  HIP_OK(launch_population_delta(out, weights, frozen, n_directions, n_params, seed, offset,
+                                 (double*)workspace, st));
+  return 0;
+}
+
 }  // extern "C"

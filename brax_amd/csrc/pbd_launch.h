@@ -224,6 +224,14 @@ hipError_t launch_env_policy_single(int L, int feat, int gw, int tpb, int64_t n_
 hipError_t launch_normal_slabs(float* out, int64_t slab_n, int64_t n_slabs, uint64_t seed,
                                uint64_t offset, uint64_t slab_stride, const int64_t* epoch,
                                uint64_t epoch_stride, hipStream_t s);
+// the evolution agents' perturbation and weighted noise sum, the noise
+// regenerated on chip (pbd_evolution.hip); part: chunks x n doubles
+hipError_t launch_population_perturb(float* rows, const float* theta, const uint8_t* frozen,
+                                     int64_t P, int64_t n, int64_t stride, double sigma,
+                                     uint64_t seed, uint64_t offset, int antithetic, hipStream_t s);
+hipError_t launch_population_delta(float* out, const float* w, const uint8_t* frozen, int64_t P,
+                                   int64_t n, uint64_t seed, uint64_t offset, double* part,
+                                   hipStream_t s);
 // whole evaluations (env_step_body's EVL): the policy form (pbd_eval.hip) and
 // the open-loop form (pbd_eval_open.hip)
 hipError_t launch_env_eval_policy(int L, int feat, int gw, int tpb, int64_t n_envs, size_t lds,

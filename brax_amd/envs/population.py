@@ -10,13 +10,16 @@ things: `cumulative_reward += (reward - reward_shift) * active` with `active
 `run_episode` through `bx_env_eval_population`: env e reads its own parameter
 row, the sums and the observation moments stay on chip, and the launch writes
 one state block, `M + 3` floats and `2 O + 1` moment words per env, whatever K
-is. The optimiser halves (fitness shaping, top directions, Adam) stay with the
-caller.
+is. The optimiser halves (fitness shaping, top directions, Adam) are
+`brax_amd.training.es` and `brax_amd.training.ars`.
 
 `PolicyPopulation` owns the `(n_members, stride)` parameter rows and writes
-the perturbations from the counter RNG, so the caller's update regenerates the
-noise (`noise`) instead of keeping it. `update_running_statistics` finishes the
-normaliser's update from the on-chip moments.
+the perturbations from the counter RNG, so the update regenerates the noise
+instead of keeping it: `perturb_` (`bx_population_perturb`) and
+`weighted_noise_sum` (`bx_population_delta`) draw eps on chip and touch only
+the rows and the `(n_params,)` sum; `noise` materialises it for the chained
+forms. `update_running_statistics` finishes the normaliser's update from the
+on-chip moments.
 """
 import copy
 import ctypes as C
@@ -78,18 +81,102 @@ class PolicyPopulation:
     normal_slabs(eps, P * self.n_params, 1, int(seed), int(offset), 0)
     return eps
 
-  def perturb_(self, sigma: float, seed: int, offset: int = 0, antithetic: bool = True):
+  def _frozen(self, frozen):
+    """`frozen` as (n_params,) uint8 on the rows' device (None stays None)."""
+    if frozen is None:
+      return None
+    f = torch.as_tensor(frozen)
+    if f.numel() != self.n_params:
+      raise ValueError(f'frozen holds {f.numel()} flags, the policy {self.n_params} parameters')
+    return (f.reshape(-1) != 0).to(self.rows.device, torch.uint8).contiguous()
+
+  def _fused(self, fused, what):
+    if fused is None:
+      return self.rows.is_cuda
+    if fused and not self.rows.is_cuda:
+      raise NotImplementedError(f'no fused {what}: the rows live on {self.rows.device}')
+    return bool(fused)
+
+  def perturb_(self, sigma: float, seed: int, offset: int = 0, antithetic: bool = True,
+               frozen=None, fused: Optional[bool] = None):
     """Rows 0..P-1 = theta + sigma eps and, antithetic, rows P..2P-1 = theta -
     sigma eps (the reference's `add_noise` and concatenate; otherwise all n
     rows take theta + sigma eps), each one float32 rounding of the float64
-    expression."""
+    expression.
+
+    `frozen` (n_params,) marks parameters every row takes from theta
+    unperturbed (their counters are skipped). `fused`: None writes device rows
+    with one `bx_population_perturb` launch, which regenerates eps on chip and
+    touches only the rows, and takes the torch expression below otherwise;
+    False forces the torch expression (the same bits); True raises
+    NotImplementedError for rows off the device."""
     P = self._directions(antithetic)
+    frozen = self._frozen(frozen)
+    if self._fused(fused, 'perturbation'):
+      theta = self.policy.params
+      if theta.device != self.rows.device or theta.dtype != torch.float32 or not theta.is_contiguous():
+        raise ValueError(f'the policy buffer must be contiguous float32 on {self.rows.device}')
+      _native.check(_native.lib().bx_population_perturb(
+          self.rows.data_ptr(), theta.data_ptr(), P, self.n_params, self.stride, float(sigma),
+          int(seed), int(offset), int(bool(antithetic)),
+          None if frozen is None else frozen.data_ptr(), _stream(self.rows.device.index)))
+      return self
     step = float(sigma) * self.noise(seed, offset, antithetic).to(torch.float64)
     theta = self.policy.params.to(torch.float64)
-    self.rows[:P, :self.n_params] = (theta + step).to(torch.float32)
+    keep = None if frozen is None else frozen.bool()
+    halves = [(slice(0, P), theta + step)]
     if antithetic:
-      self.rows[P:, :self.n_params] = (theta - step).to(torch.float32)
+      halves.append((slice(P, None), theta - step))
+    for rows, value in halves:
+      value = value.to(torch.float32)
+      if keep is not None:
+        value = torch.where(keep, self.policy.params, value)
+      self.rows[rows, :self.n_params] = value
     return self
+
+  def delta_workspace(self, antithetic: bool = True):
+    """A workspace `weighted_noise_sum` takes, for a caller that sums every
+    epoch: the library states the size, this allocates it."""
+    P = self._directions(antithetic)
+    need = C.c_int64(0)
+    _native.check(_native.lib().bx_population_delta(None, None, P, self.n_params, 0, 0, None, None,
+                                                    C.byref(need), None))
+    return torch.empty((max(need.value // 8, 1),), dtype=torch.float64, device=self.rows.device)
+
+  def weighted_noise_sum(self, weights, seed: int, offset: int = 0, antithetic: bool = True,
+                         frozen=None, fused: Optional[bool] = None, workspace=None):
+    """sum_p weights[p] eps[p] over the P directions of `perturb_(sigma, seed,
+    offset, antithetic)`: `(n_params,)` float32, the float64 sum rounded once;
+    zeros where `frozen`.
+
+    `fused`: None takes `bx_population_delta` for device rows (eps regenerated
+    on chip, a fixed summation order: the same bits from run to run), else the
+    chained form `(weights.double()[:, None] * noise.double()).sum(0).float()`
+    over `noise()`; False forces the chained form; True raises
+    NotImplementedError for rows off the device. `workspace`: a contiguous
+    float64 device tensor of at least `delta_workspace()`'s size to hold the
+    kernel's partials (None: allocated per call)."""
+    P = self._directions(antithetic)
+    dev = self.rows.device
+    w = torch.as_tensor(weights).to(dev, torch.float32).reshape(-1).contiguous()
+    if w.numel() != P:
+      raise ValueError(f'{w.numel()} weights for {P} directions')
+    frozen = self._frozen(frozen)
+    if not self._fused(fused, 'weighted noise sum'):
+      s = (w.double()[:, None] * self.noise(seed, offset, antithetic).double()).sum(0).float()
+      return s if frozen is None else torch.where(frozen.bool(), torch.zeros_like(s), s)
+    if workspace is None:
+      workspace = self.delta_workspace(antithetic)
+    if (workspace.device != dev or workspace.dtype != torch.float64
+        or not workspace.is_contiguous()):
+      raise ValueError(f'workspace must be contiguous float64 on {dev}')
+    out = torch.empty((self.n_params,), dtype=torch.float32, device=dev)
+    size = C.c_int64(workspace.numel() * 8)
+    _native.check(_native.lib().bx_population_delta(
+        out.data_ptr(), w.data_ptr(), P, self.n_params, int(seed), int(offset),
+        None if frozen is None else frozen.data_ptr(), workspace.data_ptr(), C.byref(size),
+        _stream(dev.index)))
+    return out
 
   def member(self, i: int) -> MLPPolicy:
     """An `MLPPolicy` over row i (a view: it sees later `set_` / `perturb_`)."""

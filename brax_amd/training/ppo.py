@@ -73,6 +73,17 @@ class RunningStatistics:
     self.mean, self.summed_variance, self.count, self.std = update_running_statistics(
         self.mean, self.summed_variance, self.count,
         (d.sum(0), (d * d).sum(0), np.array([rows.shape[0]], np.float64)))
+    return self._publish()
+
+  def update_from_moments(self, result):
+    """The same update from a `PopulationResult`'s on-chip moments (each step
+    weighted by the env's `active`), centred on `mean_t` as the acting policy
+    read it."""
+    self.mean, self.summed_variance, self.count, self.std = update_running_statistics(
+        self.mean, self.summed_variance, self.count, result)
+    return self._publish()
+
+  def _publish(self):
     self.mean_t.copy_(torch.as_tensor(self.mean, dtype=torch.float32))
     self.std_t.copy_(torch.as_tensor(self.std, dtype=torch.float32))
     return self

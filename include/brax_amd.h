@@ -693,6 +693,53 @@ int bx_compute_gae(int64_t n_steps, int64_t n_envs, const bx_seq* reward, const 
                    const bx_seq* vs, const bx_seq* advantages, float reward_scaling,
                    float discount, float lambda, void* stream);
 
+/* The optimiser side of the evolution agents (ES, ARS), the parameter noise
+ * regenerated from the counter RNG instead of stored: direction p's noise for
+ * parameter j is eps[p, j] = N(seed, offset + 2 (p * n_params + j)), exactly
+ * the sample bx_normal_slabs(out, P * n_params, 1, seed, offset, ...) writes
+ * at out[p * n_params + j]. No system handle: the launches go to the device
+ * that owns `stream` (the current device for NULL). (Additive: no ABI bump.)
+ *
+ * bx_population_perturb writes the population's rows in one launch:
+ *   rows[p * stride + j]                  = (float)((double)theta[j] + sigma * (double)eps[p, j])
+ *   rows[(n_directions + p) * stride + j] = (float)((double)theta[j] - sigma * (double)eps[p, j])
+ * (the second only when `antithetic`), p < n_directions, j < n_params; the
+ * float64 product and the sum are each rounded on their own (no fused
+ * multiply-add). The words j >= n_params of a row (stride padding) are not
+ * written. `frozen` (NULL: none) is n_params device bytes: where frozen[j] is
+ * not 0 every row gets theta[j] itself; the counters of a frozen j are
+ * skipped, not reused. Rows whose base and stride are 16-byte aligned are
+ * written with 16-byte stores. A null `rows` or `theta`, n_directions < 1,
+ * n_params < 1, stride < n_params, more than 2^40 samples, or rows that
+ * overlap theta fail. */
+int bx_population_perturb(float* rows, const float* theta, int64_t n_directions, int64_t n_params,
+                          int64_t stride, double sigma, uint64_t seed, uint64_t offset,
+                          int antithetic, const uint8_t* frozen, void* stream);
+
+/* out[j] = (float) sum_{p < n_directions} (double)weights[p] * (double)eps[p, j],
+ * `weights` (n_directions,) float32 on the device, the same eps. The sum is
+ * float64 in a fixed order that depends on (n_directions, n_params) alone, so
+ * it is the same bit for bit from run to run (no floating-point atomics): the
+ * directions are split into chunks of BX_POPULATION_DELTA_CHUNK, one
+ * workgroup row per chunk, each chunk summed in ascending p, and the chunk
+ * partials are summed in ascending chunk order. A direction whose weight is
+ * +-0 is skipped (eps is finite, so its term is an exact zero); a NaN or Inf
+ * weight makes every non-frozen out[j] non-finite. frozen[j] != 0 gives
+ * out[j] = 0.
+ *
+ * The partials live in the caller's `workspace` (device memory, 8-byte
+ * aligned) of *workspace_bytes bytes; the library keeps no scratch of its
+ * own. With workspace == NULL the call launches nothing and writes the size
+ * it needs to *workspace_bytes: 8 * n_params * ceil(n_directions /
+ * BX_POPULATION_DELTA_CHUNK). With a workspace, *workspace_bytes below that
+ * size or a misaligned workspace fails. A null `workspace_bytes`, a null
+ * `out` or `weights` with a workspace, n_directions < 1, n_params < 1 or more
+ * than 2^40 samples fail. */
+#define BX_POPULATION_DELTA_CHUNK 64
+int bx_population_delta(float* out, const float* weights, int64_t n_directions, int64_t n_params,
+                        uint64_t seed, uint64_t offset, const uint8_t* frozen, void* workspace,
+                        int64_t* workspace_bytes, void* stream);
+
 /*
  * Standalone HBM-streaming phase kernels over a structure-of-arrays batch
  * (the integrator and collider phases benchmarked in isolation).
