@@ -162,7 +162,12 @@ POPULATION_DELTA_ARGS = (
     ('out', _vp), ('weights', _vp), ('n_directions', C.c_int64), ('n_params', C.c_int64),
     ('seed', C.c_uint64), ('offset', C.c_uint64), ('frozen', _vp), ('workspace', _vp),
     ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
-ARGS = {'bx_env_eval_policy': EVAL_POLICY_ARGS, 'bx_env_eval_packed': EVAL_PACKED_ARGS,
+PLAN_FIELDS = ('mode', 'lanes', 'lds_bytes', 'feat', 'gw', 'fold', 'jb', 'cb')  # bx_system_blob
+SYSTEM_BLOB_ARGS = (
+    ('desc', _vp), ('reset', _vp), ('words', C.POINTER(C.c_uint32)), ('capacity', C.c_int64),
+    ('n_words', C.POINTER(C.c_int64)), ('plan', C.POINTER(C.c_int32)))
+ARGS = {'bx_system_blob': SYSTEM_BLOB_ARGS,
+        'bx_env_eval_policy': EVAL_POLICY_ARGS, 'bx_env_eval_packed': EVAL_PACKED_ARGS,
         'bx_env_eval_population': EVAL_POPULATION_ARGS, 'bx_compute_gae': COMPUTE_GAE_ARGS,
         'bx_population_perturb': POPULATION_PERTURB_ARGS,
         'bx_population_delta': POPULATION_DELTA_ARGS}

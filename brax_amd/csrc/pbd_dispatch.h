@@ -4,7 +4,7 @@
 // features, gather width) that exist. The launchers' switches are generated
 // from the list (pbd_launch.h), so a variant cannot be selected without
 // being instantiated; the host asks the same function which kernel a system
-// gets (single_kernel_feat: bx_capi.cpp sizes the staged limit rows by it).
+// gets (bx_blob.cpp sizes the staged limit rows by its F_SPH bit).
 // Single mode at 16 lanes is specialised per feature set and gather width.
 //
 // kind_variant() is the same for the env kinds with kernels of their own
@@ -99,7 +99,7 @@ constexpr int single_key(int L, int F, int M) { return (L << 16) | (F << 4) | M;
 // ---------------------------------------------------------------------------
 // the env kinds' own kernels
 // ---------------------------------------------------------------------------
-// what bx_capi.cpp's plan allows the env kernels (the launchers' `fold`):
+// what bx_blob.cpp's plan allows the env kernels (the launchers' `fold`):
 // FOLD_DAMPING = every joint j has torque actuator j, so the kind kernels fold
 // each joint's damping into its actuator's slot (no kind kernel without it);
 // FOLD_BODY_COPIES = the joint-halves kernels may give each side lane its

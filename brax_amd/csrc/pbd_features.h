@@ -48,7 +48,7 @@ enum { F_LEAN = F_CC | F_TW };
 // pbd_step_single) resolve each body's one contact row on the body's own
 // lanes: joint halves, one collider group, one-way capsule-plane rows only,
 // one row slot and no forces (the Ant env kernels). The host admits a system
-// to such a kernel only when its rows fit (bx_capi.cpp cb_rows_ok).
+// to such a kernel only when its rows fit (bx_blob.cpp cb_rows_ok).
 // A/B switch -DBX_NO_CB: the same kernels with the row-lane passes.
 constexpr bool cb_feat(int F) {
 #if defined(BX_NO_CB)

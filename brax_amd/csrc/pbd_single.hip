@@ -59,7 +59,6 @@ hipError_t launch_system_step_single(int L, int feat, int gw, int tpb, int64_t n
   }
   return hipGetLastError();
 }
-int single_kernel_feat(int L, int feat, int gw) { return single_variant(L, feat, gw).F; }
 
 // the unit's family: step_kernel's choice (pbd_dispatch.h) among the five
 // kernel templates above; the wide kernels exist for Ant only, the rollout

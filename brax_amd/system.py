@@ -109,6 +109,22 @@ class Body:
     self.idx = np.arange(len(self.mass))
 
 
+def desc_blob(desc, reset_desc, num_joint_dof=None):
+  """bx_system_blob of a descriptor and a reset descriptor (None: no reset
+  tables): (np.uint32 words, plan dict)."""
+  cd, keep = abi.make_desc(desc)
+  rd, keep_r = abi.make_reset_desc(reset_desc, num_joint_dof) if reset_desc else (None, None)
+  rp = C.byref(rd) if rd is not None else None
+  n, plan = C.c_int64(), (C.c_int32 * len(abi.PLAN_FIELDS))()
+  fn = _native.lib().bx_system_blob
+  _native.check(fn(C.byref(cd), rp, None, 0, C.byref(n), plan))
+  words = np.zeros(n.value, np.uint32)
+  _native.check(fn(C.byref(cd), rp, words.ctypes.data_as(C.POINTER(C.c_uint32)), n.value,
+                   C.byref(n), plan))
+  del keep, keep_r
+  return words, dict(zip(abi.PLAN_FIELDS, (int(v) for v in plan)))
+
+
 class System:
   """A brax system compiled for the MI355X kernels."""
 
@@ -185,6 +201,15 @@ class System:
     return {'mode': mode.value, 'lanes': lanes.value, 'lds_bytes': per_wg,
             'envs_per_cu_by_lds': by_lds, 'envs_per_cu_by_registers': by_regs,
             'envs_per_cu': runs}
+
+  @staticmethod
+  def blob(config):
+    """The blob `config` compiles to, on the host without a device
+    (bx_system_blob): (np.uint32 words, the BlobHdr first; {'mode', 'lanes',
+    'lds_bytes', 'feat', 'gw', 'fold', 'jb', 'cb'})."""
+    vc, desc, meta = compiler.compile_system(config)
+    rdesc = compiler.compile_reset(vc, meta['body_index'])
+    return desc_blob(desc, rdesc, meta['num_joint_dof'])
 
   def _create(self, reset_desc):
     cd, keep = abi.make_desc(self.desc)

@@ -320,6 +320,14 @@ int bx_system_env_lanes(bx_system* sys);
 int bx_system_plan(const bx_desc* desc, const bx_reset_desc* reset, int32_t* mode,
                    int32_t* lanes, int32_t* lds_bytes);
 
+/* The same host half with its product: the blob bx_system_create would copy
+ * to the device (n_words 32-bit words, the BlobHdr first) and the whole plan,
+ * plan = {mode, lanes, lds_bytes, feat, gw, fold, jb, cb}. words may be NULL
+ * to ask only for n_words and the plan; a capacity (in words) below n_words is
+ * an error. No device. */
+int bx_system_blob(const bx_desc* desc, const bx_reset_desc* reset, uint32_t* words,
+                   int64_t capacity, int64_t* n_words, int32_t plan[8]);
+
 /* LDS bytes per workgroup of this system's System.step kernel (the current
  * variant): with 160 KB per CU it sets how many envs a CU holds at once (the
  * large-scene kernel runs one env per 256-thread workgroup). A diagnostic

@@ -1,5 +1,5 @@
 """Which systems the Ant env kernels may resolve contacts for on the body
-lanes (CB, pbd_features.h cb_feat; bx_capi.cpp cb_rows_ok), as build_blob
+lanes (CB, pbd_features.h cb_feat; bx_blob.cpp cb_rows_ok), as build_plan
 reports it under BX_PLAN_DEBUG: `contact_on_body=1` needs the body copies (JB)
 and one collider group of one-way capsule-plane rows against bodies on no
 joint side, at most one row per body. Every other system keeps the row-lane

@@ -1,7 +1,7 @@
 """Per-phase lane use of the SINGLE-mode env kernels (diagnostic), next to the
 static per-phase instruction mix (tools/phase_mix.py): for each phase of one
 substep, the lanes of an env's 16 that execute it and the distinct items
-they cover, from the compiled system (the lane roles of bx_capi.cpp's lane
+they cover, from the compiled system (the lane roles of bx_blob.cpp's lane
 image: joint halves put joint j's parent side on lane j and its child side
 on lane j + 8; with body copies (JB) every side lane integrates its side's
 body; contact rows sit one per lane).
