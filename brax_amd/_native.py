@@ -96,6 +96,8 @@ _SIGS = {
     'bx_compute_gae': abi.SIGNATURES['bx_compute_gae'],
     'bx_population_perturb': abi.SIGNATURES['bx_population_perturb'],
     'bx_population_delta': abi.SIGNATURES['bx_population_delta'],
+    'bx_replay_insert': abi.SIGNATURES['bx_replay_insert'],
+    'bx_replay_sample': abi.SIGNATURES['bx_replay_sample'],
 }
 
 EXPORTS = tuple(_SIGS)

@@ -162,6 +162,24 @@ POPULATION_DELTA_ARGS = (
     ('out', _vp), ('weights', _vp), ('n_directions', C.c_int64), ('n_params', C.c_int64),
     ('seed', C.c_uint64), ('offset', C.c_uint64), ('frozen', _vp), ('workspace', _vp),
     ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
+FIELDS_MAX = 8  # BX_FIELDS_MAX
+
+
+class BxFields(C.Structure):
+  """A batch of rows held as up to FIELDS_MAX float32 arrays: row r is the
+  concatenation of the width[f] floats at ptr[f] + r * row_stride[f]."""
+  _fields_ = [('n_fields', C.c_int32), ('ptr', C.c_void_p * FIELDS_MAX),
+              ('width', C.c_int64 * FIELDS_MAX), ('row_stride', C.c_int64 * FIELDS_MAX)]
+
+
+_fields = C.POINTER(BxFields)
+REPLAY_INSERT_ARGS = (
+    ('data', _vp), ('capacity', C.c_int64), ('row_words', C.c_int64), ('position', C.c_int64),
+    ('n_rows', C.c_int64), ('src', _fields), ('stream', _vp))
+REPLAY_SAMPLE_ARGS = (
+    ('data', _vp), ('capacity', C.c_int64), ('row_words', C.c_int64), ('position', C.c_int64),
+    ('size', C.c_int64), ('n_samples', C.c_int64), ('seed', C.c_uint64), ('offset', C.c_uint64),
+    ('dst', _fields), ('idx_out', _vp), ('stream', _vp))
 PLAN_FIELDS = ('mode', 'lanes', 'lds_bytes', 'feat', 'gw', 'fold', 'jb', 'cb')  # bx_system_blob
 SYSTEM_BLOB_ARGS = (
     ('desc', _vp), ('reset', _vp), ('words', C.POINTER(C.c_uint32)), ('capacity', C.c_int64),
@@ -170,7 +188,8 @@ ARGS = {'bx_system_blob': SYSTEM_BLOB_ARGS,
         'bx_env_eval_policy': EVAL_POLICY_ARGS, 'bx_env_eval_packed': EVAL_PACKED_ARGS,
         'bx_env_eval_population': EVAL_POPULATION_ARGS, 'bx_compute_gae': COMPUTE_GAE_ARGS,
         'bx_population_perturb': POPULATION_PERTURB_ARGS,
-        'bx_population_delta': POPULATION_DELTA_ARGS}
+        'bx_population_delta': POPULATION_DELTA_ARGS,
+        'bx_replay_insert': REPLAY_INSERT_ARGS, 'bx_replay_sample': REPLAY_SAMPLE_ARGS}
 SIGNATURES = {name: ([t for _, t in args], C.c_int) for name, args in ARGS.items()}
 
 

@@ -13,6 +13,7 @@
 #include "pbd_features.h"
 #include "pbd_launch.h"
 #include "pbd_layout.h"
+#include "replay_launch.h"
 #include "train_launch.h"
 
 using namespace bx;
@@ -1093,6 +1094,94 @@ int bx_population_delta(float* out, const float* weights, int64_t n_directions, 
   if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
   HIP_OK(launch_population_delta(out, weights, frozen, n_directions, n_params, seed, offset,
                                  (double*)workspace, st));
+  return 0;
+}
+
+namespace {
+
+// the checks bx_replay_insert and bx_replay_sample share, and the kernels'
+// field table: prefix offsets, and each field's pointer moved back by its
+// offset so a row word indexes it directly
+int replay_args(const float* data, int64_t capacity, int64_t row_words, int64_t position,
+                int64_t n, const bx_fields* f, ReplayArgs* a) {
+  if (!data || !f) return fail("null argument");
+  if (f->n_fields < 0 || f->n_fields > BX_FIELDS_MAX)
+    return fail("n_fields " + std::to_string(f->n_fields) + " outside 0.." +
+                std::to_string(BX_FIELDS_MAX));
+  if (capacity < 1) return fail("capacity must be >= 1");
+  if (row_words < 0 || row_words > (1 << 24)) return fail("row_words outside 0..2^24");
+  if (capacity > ((int64_t)1 << 40) / (row_words ? row_words : 1)) return fail("ring too large");
+  if (position < 0 || position >= capacity) return fail("position outside the ring");
+  int64_t total = 0;
+  for (int k = 0; k < f->n_fields; ++k) {
+    if (f->width[k] < 0 || f->width[k] > (1 << 24)) return fail("field width outside 0..2^24");
+    total += f->width[k];
+  }
+  if (total != row_words)
+    return fail("field widths sum to " + std::to_string(total) + ", row_words is " +
+                std::to_string(row_words));
+  int64_t sum = 0;
+  for (int k = 0; k < f->n_fields; ++k) {
+    if (!f->ptr[k]) return fail("null field pointer");
+    a->off[k] = (int32_t)sum;
+    a->base[k] = (float*)((uintptr_t)f->ptr[k] - (uintptr_t)sum * sizeof(float));
+    a->stride[k] = f->row_stride[k];
+    sum += f->width[k];
+  }
+  for (int k = f->n_fields; k < BX_FIELDS_MAX; ++k) {  // selected by no word
+    a->off[k] = (int32_t)row_words;
+    a->base[k] = nullptr;
+    a->stride[k] = 0;
+  }
+  a->data = const_cast<float*>(data);
+  a->capacity = capacity;
+  a->position = position;
+  a->row_words = (int32_t)row_words;
+  a->n = n;
+  return 0;
+}
+
+}  // namespace
+
+int bx_replay_insert(float* data, int64_t capacity, int64_t row_words, int64_t position,
+                     int64_t n_rows, const bx_fields* src, void* stream) {
+  if (n_rows < 0) return fail("negative n_rows");
+  if (n_rows == 0) return 0;
+  ReplayArgs a{};
+  if (replay_args(data, capacity, row_words, position, n_rows, src, &a)) return 1;
+  if (n_rows > capacity)
+    return fail("n_rows " + std::to_string(n_rows) + " above the capacity " +
+                std::to_string(capacity));
+  int dev = -1;
+  hipStream_t st = as_stream(stream);
+  if (st) HIP_OK(hipStreamGetDevice(st, &dev));
+  else HIP_OK(hipGetDevice(&dev));
+  DeviceScope scope(dev);
+  if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
+  HIP_OK(launch_replay_insert(a, st));
+  return 0;
+}
+
+int bx_replay_sample(const float* data, int64_t capacity, int64_t row_words, int64_t position,
+                     int64_t size, int64_t n_samples, uint64_t seed, uint64_t offset,
+                     const bx_fields* dst, int64_t* idx_out, void* stream) {
+  if (n_samples < 0) return fail("negative n_samples");
+  if (n_samples == 0) return 0;
+  ReplayArgs a{};
+  if (replay_args(data, capacity, row_words, position, n_samples, dst, &a)) return 1;
+  if (size < 1 || size > capacity)
+    return fail("size " + std::to_string(size) + " outside 1.." + std::to_string(capacity));
+  a.size = size;
+  a.seed = seed;
+  a.offset = offset;
+  a.idx_out = idx_out;
+  int dev = -1;
+  hipStream_t st = as_stream(stream);
+  if (st) HIP_OK(hipStreamGetDevice(st, &dev));
+  else HIP_OK(hipGetDevice(&dev));
+  DeviceScope scope(dev);
+  if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
+  HIP_OK(launch_replay_sample(a, st));
   return 0;
 }
 

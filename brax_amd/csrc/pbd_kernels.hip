@@ -25,6 +25,7 @@
 
 #include <type_traits>
 
+#include "bx_mix.h"
 #include "pbd_features.h"
 #include "pbd_launch.h"
 #include "pbd_layout.h"
@@ -4104,10 +4105,7 @@ __device__ __forceinline__ constexpr bool ek_has(int k) {
 
 // counter-based uniform: splitmix64 of (seed, global index) -> [lo, hi)
 __device__ __forceinline__ float uniform_at(uint64_t seed, uint64_t i, float lo, float hi) {
-  uint64_t z = seed * 0x9E3779B97F4A7C15ull + i + 0x632BE59BD9B4E019ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z = z ^ (z >> 31);
+  const uint64_t z = mix64(seed, i);
   float u = (float)(z >> 40) * (1.0f / 16777216.0f);
   return lo + (hi - lo) * u;
 }

@@ -1,13 +1,17 @@
 """The learner side (`brax/training`): PPO on the fused rollouts, ES and ARS
-on the one-launch population episode.
+on the one-launch population episode, SAC on a device replay queue.
 
-    from brax_amd.training import ars, es, ppo
+    from brax_amd.training import ars, es, ppo, sac
     make_policy, params, metrics = ppo.train('ant', num_timesteps=..., episode_length=1000, ...)
     make_policy, params, metrics = es.train('ant', num_timesteps=..., population_size=4096, ...)
     make_policy, params, metrics = ars.train('ant', num_timesteps=..., number_of_directions=60, ...)
+    make_policy, params, metrics = sac.train('ant', num_timesteps=..., min_replay_size=8192, ...)
 """
-from brax_amd.training import ars, es, gae, losses, networks, ppo
+from brax_amd.training import (ars, es, gae, losses, networks, ppo, replay_buffers, sac, sac_losses,
+                               sac_networks)
 from brax_amd.training.gae import compute_gae
 from brax_amd.training.losses import Transition, ppo_loss
 from brax_amd.training.networks import make_ppo_networks, mlp
+from brax_amd.training.replay_buffers import UniformSamplingQueue, transition_fields
+from brax_amd.training.sac_networks import make_sac_networks
 from brax_amd.training.ppo import Learner, RunningStatistics, step_accounting, train, transitions

@@ -748,6 +748,60 @@ int bx_population_delta(float* out, const float* weights, int64_t n_directions, 
                         uint64_t seed, uint64_t offset, const uint8_t* frozen, void* workspace,
                         int64_t* workspace_bytes, void* stream);
 
+/* A batch of rows held as up to BX_FIELDS_MAX separate fp32 arrays: row r of
+ * the batch is the concatenation, in field order, of the width[f] floats at
+ * ptr[f] + r * row_stride[f] (strides in floats; a field may be a column
+ * slice of a wider buffer, row_stride[f] > width[f]). The widths sum to the
+ * row's length in words. */
+#define BX_FIELDS_MAX 8
+typedef struct bx_fields {
+  int32_t n_fields;
+  float* ptr[BX_FIELDS_MAX];
+  int64_t width[BX_FIELDS_MAX];
+  int64_t row_stride[BX_FIELDS_MAX];
+} bx_fields;
+
+/* The replay queue of the off-policy learner (the reference's
+ * `UniformSamplingQueue`, training/replay_buffers.py:92-131, :200-215): a ring
+ * `data` of `capacity` rows of `row_words` fp32 words, contiguous. The ring's
+ * control numbers (`position`, the next row to write, 0 <= position <
+ * capacity, and `size`, the live rows) are the caller's and pass by value. No
+ * system handle: the launches go to the device that owns `stream` (the current
+ * device for NULL). Both kernels only copy 32-bit words, so NaN payloads and
+ * any other bit pattern arrive unchanged. (Additive: no ABI bump.)
+ *
+ * bx_replay_insert writes batch row r of `src` to ring row (position + r) mod
+ * capacity, r < n_rows, in one launch: the ring wraps inside the batch and is
+ * never rolled. The caller then advances position by n_rows mod capacity and
+ * size to min(size + n_rows, capacity). A null `data` or `src` or field
+ * pointer with n_rows > 0, n_fields above BX_FIELDS_MAX, a negative width,
+ * widths that do not sum to row_words, a position outside [0, capacity) or
+ * n_rows > capacity fail; n_rows = 0 launches nothing. `src` must not overlap
+ * `data`. */
+int bx_replay_insert(float* data, int64_t capacity, int64_t row_words, int64_t position,
+                     int64_t n_rows, const bx_fields* src, void* stream);
+
+/* bx_replay_sample draws n_samples rows uniformly with replacement from the
+ * `size` live rows, the oldest of which is ring row (position - size) mod
+ * capacity, and scatters sample j into row j of `dst`'s fields, in one launch:
+ *   z   = mix(seed, offset + j)            (uint64 arithmetic, wrapping)
+ *   k   = (z * size) >> 64                 (the high half of the 128-bit product)
+ *   row = (position - size + k) mod capacity
+ * with mix the counter RNG's 64-bit splitmix64 finaliser (bx_uniform's bits
+ * before their top 24 are taken):
+ *   z = seed * 0x9E3779B97F4A7C15 + i + 0x632BE59BD9B4E019
+ *   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *   z = z ^ (z >> 31)
+ * so the rows are a pure function of (seed, offset, position, size,
+ * capacity). idx_out (NULL: not wanted) receives the n_samples ring rows as
+ * int64. The failures of bx_replay_insert (with `dst` for `src`, n_samples for
+ * n_rows, without the n_rows bound), and size < 1 or size > capacity, fail;
+ * n_samples = 0 launches nothing. `dst` must not overlap `data`. */
+int bx_replay_sample(const float* data, int64_t capacity, int64_t row_words, int64_t position,
+                     int64_t size, int64_t n_samples, uint64_t seed, uint64_t offset,
+                     const bx_fields* dst, int64_t* idx_out, void* stream);
+
 /*
  * Standalone HBM-streaming phase kernels over a structure-of-arrays batch
  * (the integrator and collider phases benchmarked in isolation).

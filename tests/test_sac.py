@@ -1,0 +1,508 @@
+"""SAC and its replay queue without a GPU: the ABI mirror and refusals of
+`bx_replay_insert` / `bx_replay_sample`, the chained queue against a numpy
+restatement of the reference's roll-based `QueueBase.insert`
+(`training/replay_buffers.py:92-131`), the sampler's index formula against
+Python-int arithmetic, the three losses against a float64 numpy restatement
+of `training/agents/sac/losses.py`, `sgd_step`'s ordering, and `train`'s step
+accounting."""
+import ctypes as C
+import functools
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from brax_amd import _native, abi
+from brax_amd.training import replay_buffers, sac, sac_losses, sac_networks
+from brax_amd.training.replay_buffers import UniformSamplingQueue, transition_fields
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+M64 = (1 << 64) - 1
+
+
+# ---- ABI ------------------------------------------------------------------------------------
+
+def _header_args(src, name):
+  m = re.search(r'^int %s\s*\(([^;]*)\);' % name, src, re.M)
+  assert m, name
+  return [re.match(r'\s*(.*?)(\w+)\s*$', a).group(2) for a in m.group(1).replace('\n', ' ').split(',')]
+
+
+def test_header_abi_and_exports():
+  src = open(os.path.join(ROOT, 'include', 'brax_amd.h')).read()
+  for name in ('bx_replay_insert', 'bx_replay_sample'):
+    assert _header_args(src, name) == [n for n, _ in abi.ARGS[name]]
+    assert name in _native.EXPORTS
+  body = re.search(r'typedef struct bx_fields \{(.*?)\} bx_fields;', src, re.S).group(1)
+  assert re.findall(r'(\w+)(?:\[BX_FIELDS_MAX\])?;', body) == [f for f, _ in abi.BxFields._fields_]
+  assert '#define BX_FIELDS_MAX 8' in src and abi.FIELDS_MAX == 8
+  assert abi.ABI_VERSION == 14 and '#define BX_ABI_VERSION 14' in src
+  assert _native.lib().bx_abi_version() == 14
+
+
+def test_refusals_before_any_launch():
+  """Every refusal sets bx_last_error and returns before a device call (the
+  pointers here are host memory: a launch would fault)."""
+  lib = _native.lib()
+  buf = (C.c_float * 64)()
+  p = C.addressof(buf)
+
+  def fields(widths, ptr=p, n=None):
+    f = abi.BxFields()
+    f.n_fields = len(widths) if n is None else n
+    for k, w in enumerate(widths[:8]):
+      f.ptr[k], f.width[k], f.row_stride[k] = ptr, w, w
+    return f
+  ok = fields([3, 2])
+  insert = lambda data, cap, words, pos, n, f: lib.bx_replay_insert(  # noqa: E731
+      data, cap, words, pos, n, None if f is None else C.byref(f), None)
+  sample = lambda data, cap, words, pos, size, n, f: lib.bx_replay_sample(  # noqa: E731
+      data, cap, words, pos, size, n, 0, 0, None if f is None else C.byref(f), None, None)
+  nine = fields([1] * 8, n=9)
+  cases = [
+      (insert, (None, 4, 5, 0, 2, ok), b'null'),
+      (insert, (p, 4, 5, 0, 2, None), b'null'),
+      (insert, (p, 4, 5, 0, 2, fields([3, 2], ptr=None)), b'null field pointer'),
+      (insert, (p, 4, 6, 0, 2, ok), b'field widths sum to 5, row_words is 6'),
+      (insert, (p, 4, 9, 0, 2, nine), b'n_fields 9'),
+      (insert, (p, 4, 5, 0, 5, ok), b'n_rows 5 above the capacity 4'),
+      (insert, (p, 4, 5, 4, 2, ok), b'position'),
+      (insert, (p, 4, 5, -1, 2, ok), b'position'),
+      (insert, (p, 4, 5, 0, -1, ok), b'negative n_rows'),
+      (sample, (None, 4, 5, 0, 2, 3, ok), b'null'),
+      (sample, (p, 4, 5, 0, 2, 3, None), b'null'),
+      (sample, (p, 4, 5, 0, 2, 3, fields([3, 2], ptr=None)), b'null field pointer'),
+      (sample, (p, 4, 4, 0, 2, 3, ok), b'field widths sum to 5, row_words is 4'),
+      (sample, (p, 4, 9, 0, 2, 3, nine), b'n_fields 9'),
+      (sample, (p, 4, 5, 0, 0, 3, ok), b'size 0 outside 1..4'),
+      (sample, (p, 4, 5, 0, 5, 3, ok), b'size 5 outside 1..4'),
+      (sample, (p, 4, 5, 4, 2, 3, ok), b'position'),
+  ]
+  for fn, args, word in cases:
+    assert fn(*args) != 0 and word in lib.bx_last_error(), (args[1:-1], lib.bx_last_error())
+  # zero rows / zero samples: a successful no-op, whatever the rest
+  assert insert(None, 0, 0, 0, 0, None) == 0
+  assert sample(None, 0, 0, 0, 0, 0, None) == 0
+  assert insert(p, 4, 6, 9, 0, ok) == 0 and sample(p, 4, 6, 9, 0, 0, ok) == 0
+
+
+# ---- the queue against the reference's roll ---------------------------------------------------
+
+class _ReferenceQueue:
+  """`QueueBase.insert`, replay_buffers.py:92-131, in numpy."""
+
+  def __init__(self, capacity, words):
+    self.data = np.zeros((capacity, words), np.float32)
+    self.position = 0
+    self.size = 0
+
+  def insert(self, update):
+    data = self.data
+    if len(update) > len(data):
+      raise ValueError
+    position = self.position
+    roll = min(0, len(data) - position - len(update))
+    if roll:
+      data = np.roll(data, roll, axis=0)
+    position = position + roll
+    data[position:position + len(update)] = update
+    self.data = data
+    self.position = (position + len(update)) % len(data)
+    self.size = min(self.size + len(update), len(data))
+
+  def aged(self):
+    i = (self.position - self.size + np.arange(self.size)) % len(self.data)
+    return self.data[i]
+
+
+def _aged(q):
+  i = (q.position - q.size + torch.arange(q.size)) % q.capacity
+  return q.data[i].numpy()
+
+
+@pytest.mark.parametrize('capacity,batches', [
+    (1, [1, 1, 1]), (5, [1, 5, 2, 2, 3]), (5, [5, 5, 1]), (7, [3, 3, 3, 7, 2, 6, 6]),
+    (64, [16] * 5 + [64, 1]), (64, [24, 24, 24, 24, 63, 2]), (130, [64, 65, 3, 130, 129, 7])])
+def test_chained_insert_equals_the_references_roll(capacity, batches):
+  fields = transition_fields(3, 2)
+  words = sum(fields.values())
+  assert words == 11
+  q = UniformSamplingQueue(capacity, fields, 4)
+  ref = _ReferenceQueue(capacity, words)
+  rng = np.random.default_rng(capacity)
+  inserted = []
+  for n in batches:
+    rows = rng.normal(size=(n, words)).astype(np.float32)
+    inserted.append(rows)
+    parts = np.split(rows, np.cumsum(list(fields.values()))[:-1], axis=1)
+    batch = {k: torch.from_numpy(np.ascontiguousarray(p)) for k, p in zip(fields, parts)}
+    batch['reward'] = batch['reward'][:, 0]  # (n,) passes for a width of 1
+    q.insert(batch, fused=False)
+    ref.insert(rows)
+    assert q.size == ref.size
+    assert np.array_equal(_aged(q), ref.aged())
+    # oldest dropped first: the live rows are the last `size` inserted, in order
+    assert np.array_equal(_aged(q), np.concatenate(inserted)[-q.size:])
+  with pytest.raises(ValueError, match='larger than the maximum replay size'):
+    q.insert({k: torch.zeros((capacity + 1, w)) for k, w in fields.items()})
+  with pytest.raises(NotImplementedError):
+    q.insert({k: torch.zeros((1, w)) for k, w in fields.items()}, fused=True)  # CPU data
+
+
+def test_transition_fields_and_queue_arguments():
+  f = transition_fields(87, 8)
+  assert list(f.items()) == [('observation', 87), ('action', 8), ('reward', 1), ('discount', 1),
+                             ('next_observation', 87), ('truncation', 1)]
+  assert sum(f.values()) == 2 * 87 + 8 + 3 == 185
+  q = UniformSamplingQueue(6, f, 4, dtype=torch.float64)
+  assert tuple(q.data.shape) == (6, 185) and q.data.dtype == torch.float64
+  assert (q.position, q.size, q.counter) == (0, 0, 0)
+  with pytest.raises(ValueError):
+    q.sample()  # empty
+  with pytest.raises(ValueError):
+    q.insert({'observation': torch.zeros(2, 87)})
+  q.insert({k: torch.full((4, w), float(i)) for i, (k, w) in enumerate(f.items())})
+  with pytest.raises(NotImplementedError):
+    q.sample(fused=True)
+  s = q.sample()
+  assert q.counter == 4 and all(t.is_contiguous() and t.dtype == torch.float64 for t in s.values())
+  assert [tuple(s[k].shape) for k in f] == [(4, w) for w in f.values()]
+  assert [float(s[k][0, 0]) for k in f] == [0, 1, 2, 3, 4, 5]
+
+
+# ---- the index formula ------------------------------------------------------------------------
+
+def _mix(seed, i):
+  z = (seed * 0x9E3779B97F4A7C15 + i + 0x632BE59BD9B4E019) & M64
+  z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+  z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+  return z ^ (z >> 31)
+
+
+def reference_rows(seed, offset, n, position, size, capacity):
+  """`bx_replay_sample`'s rows in Python ints (arbitrary precision, masked)."""
+  return [(position - size + ((_mix(seed & M64, (offset + j) & M64) * size) >> 64)) % capacity
+          for j in range(n)]
+
+
+@pytest.mark.parametrize('size,position,capacity', [
+    (1, 0, 1), (1, 3, 5), (3, 1, 7), (3, 3, 3), (1 << 20, 5, 1 << 20), (1 << 20, 0, (1 << 20) + 3),
+    (1 << 31, 17, (1 << 31) + 9), (1 << 31, 0, 1 << 31)])
+def test_sample_rows_equal_python_int_arithmetic(size, position, capacity):
+  n = 16
+  for seed in (0, 7, (1 << 63) + 5, M64):
+    for offset in (0, (1 << 32) - 3, (1 << 64) - 3):  # the counter carries out of 32 and 64 bits
+      got = replay_buffers.sample_rows(seed, offset, n, position, size, capacity)
+      want = reference_rows(seed, offset, n, position, size, capacity)
+      assert got.dtype == torch.int64 and got.tolist() == want, (seed, offset)
+      live = {(position - size + k) % capacity for k in range(min(size, 64))}
+      assert all(0 <= r < capacity for r in want)
+      if size <= 64:
+        assert set(want) <= live
+  # the building blocks at the edges
+  z = torch.tensor([0, 1, -1, 1 << 62, -(1 << 63)], dtype=torch.int64)
+  for s in (1, 3, (1 << 31), (1 << 62) + 12345):
+    assert replay_buffers.mulhi64(z, s).tolist() == [((int(v) & M64) * s) >> 64 for v in z]
+
+
+def test_chained_sample_draws_live_rows_and_advances_the_counter():
+  f = {'a': 2, 'b': 1}
+  q = UniformSamplingQueue(7, f, 5, seed=11)
+  q.data.fill_(float('nan'))  # dead rows
+  q.insert({'a': torch.arange(8.).reshape(4, 2), 'b': torch.arange(4.) + 100})
+  q.insert({'a': torch.arange(8.).reshape(4, 2) + 8, 'b': torch.arange(4.) + 104})  # wraps
+  assert (q.position, q.size) == (1, 7)
+  idx = torch.empty(5, dtype=torch.int64)
+  s0 = q.sample(indices=idx)
+  assert idx.tolist() == reference_rows(11, 0, 5, 1, 7, 7) and q.counter == 5
+  assert torch.equal(s0['a'], q.data[idx, :2]) and torch.equal(s0['b'], q.data[idx, 2:])
+  s1 = q.sample(indices=idx)
+  assert idx.tolist() == reference_rows(11, 5, 5, 1, 7, 7) and q.counter == 10
+  q.counter = 0
+  again = q.sample()
+  assert all(torch.equal(again[k], s0[k]) for k in f)
+  # size < capacity: no dead row is ever drawn
+  q2 = UniformSamplingQueue(64, f, 257, seed=3)
+  q2.data.fill_(float('nan'))
+  q2.insert({'a': torch.ones(3, 2), 'b': torch.ones(3)})
+  out = {'a': torch.zeros(257, 2), 'b': torch.zeros(257)}
+  got = q2.sample(out=out)
+  assert got['a'] is out['a'] and not any(torch.isnan(t).any() for t in got.values())
+
+
+# ---- the losses -------------------------------------------------------------------------------
+
+def _np_mlp(layers, x):
+  for k, (w, b) in enumerate(layers):
+    x = x @ w + b
+    if k + 1 < len(layers):
+      x = np.maximum(x, 0)
+  return x
+
+
+def _np_softplus(x):
+  return np.logaddexp(0.0, x)
+
+
+def _np_dist(policy, obs, eps):
+  """`NormalTanhDistribution` (distribution.py:74-158): the raw sample, its
+  log-prob summed over the actions, and the post-processed action."""
+  loc, scale = np.split(_np_mlp(policy, obs), 2, axis=-1)
+  scale = _np_softplus(scale) + 0.001
+  x = loc + scale * eps
+  log_det = 2.0 * (np.log(2.0) - x - _np_softplus(-2.0 * x))
+  log_prob = (-0.5 * np.square(x / scale - loc / scale) - (0.5 * np.log(2.0 * np.pi) + np.log(scale))
+              - log_det).sum(-1)
+  return log_prob, np.tanh(x)
+
+
+def _np_q(q, obs, action):
+  hidden = np.concatenate([obs, action], axis=-1)
+  return np.concatenate([_np_mlp(c, hidden) for c in q], axis=-1)
+
+
+def _reference_losses(log_alpha, policy, q, target_q, normalizer, t, eps, reward_scaling,
+                      discounting, action_size):
+  """`make_losses`, sac/losses.py:31-96, in float64 numpy; alpha = exp(log_alpha)."""
+  norm = (lambda o: o) if normalizer is None else (lambda o: (o - normalizer[0]) / normalizer[1])
+  target_entropy = -0.5 * action_size
+  alpha = np.exp(log_alpha)
+  log_prob, _ = _np_dist(policy, norm(t['observation']), eps[0])
+  alpha_loss = np.mean(alpha * (-log_prob - target_entropy))
+  q_old_action = _np_q(q, norm(t['observation']), t['action'])
+  next_log_prob, next_action = _np_dist(policy, norm(t['next_observation']), eps[1])
+  next_q = _np_q(target_q, norm(t['next_observation']), next_action)
+  next_v = np.min(next_q, axis=-1) - alpha * next_log_prob
+  target = t['reward'] * reward_scaling + t['discount'] * discounting * next_v
+  q_error = q_old_action - target[:, None]
+  q_error = q_error * (1 - t['truncation'])[:, None]
+  critic_loss = 0.5 * np.mean(np.square(q_error))
+  log_prob, action = _np_dist(policy, norm(t['observation']), eps[2])
+  min_q = np.min(_np_q(q, norm(t['observation']), action), axis=-1)
+  actor_loss = np.mean(alpha * log_prob - min_q)
+  return alpha_loss, critic_loss, actor_loss
+
+
+def _case(seed=0, B=6, O=5, A=2, hidden=(8, 7), learning_rate=1e-2):
+  g = torch.Generator().manual_seed(seed)
+  r = lambda *s: torch.randn(s, generator=g, dtype=torch.float64)  # noqa: E731
+  factory = functools.partial(sac_networks.make_sac_networks, hidden_layer_sizes=hidden)
+  ts = sac.init_training_state(O, A, learning_rate, factory, seed + 1, dtype=torch.float64)
+  with torch.no_grad():  # zero biases would hide a wrong bias path; target != q, alpha != 1
+    for t in sac_networks.q_parameters(ts.q_layers) + sac_networks.q_parameters([ts.policy_layers]):
+      if t.dim() == 1:
+        t.copy_(r(*t.shape) * 0.1)
+    for t in sac_networks.q_parameters(ts.target_q_layers):
+      t.add_(r(*t.shape) * 0.05)
+    ts.log_alpha.fill_(-0.7)
+  done = (torch.rand((B,), generator=g) < 0.4).double()
+  trans = {'observation': r(B, O), 'action': torch.tanh(r(B, A)), 'reward': r(B, 1),
+           'discount': (1 - done)[:, None], 'next_observation': r(B, O),
+           'truncation': (done * (torch.rand((B,), generator=g) < 0.5).double())[:, None]}
+  trans['truncation'][0] = 1.0  # at least one masked row
+  normalizer = (r(O) * 0.2, torch.rand((O,), generator=g, dtype=torch.float64) + 0.5)
+  return ts, normalizer, trans, (r(B, A), r(B, A), r(B, A))
+
+
+def _n(t):
+  return t.detach().numpy().copy()
+
+
+def _np_state(ts):
+  layers = lambda ls: [(_n(w), _n(b)) for w, b in ls]  # noqa: E731
+  return dict(log_alpha=float(ts.log_alpha.detach()), policy=layers(ts.policy_layers),
+              q=[layers(c) for c in ts.q_layers], target_q=[layers(c) for c in ts.target_q_layers])
+
+
+def _np_trans(trans):
+  return {k: (_n(v)[:, 0] if v.shape[1:] == (1,) and k in ('reward', 'discount', 'truncation')
+              else _n(v)) for k, v in trans.items()}
+
+
+@pytest.mark.parametrize('with_normalizer', [True, False])
+@pytest.mark.parametrize('scaling,discounting', [(1.0, 0.9), (0.1, 0.97)])
+def test_losses_equal_the_reference_in_float64(with_normalizer, scaling, discounting):
+  ts, normalizer, trans, eps = _case()
+  if not with_normalizer:
+    normalizer = None
+  s = _np_state(ts)
+  want = _reference_losses(
+      s['log_alpha'], s['policy'], s['q'], s['target_q'],
+      None if normalizer is None else (_n(normalizer[0]), _n(normalizer[1])), _np_trans(trans),
+      [_n(e) for e in eps], scaling, discounting, 2)
+  alpha = torch.exp(ts.log_alpha.detach())
+  got = (sac_losses.alpha_loss(ts.log_alpha, ts.policy_layers, normalizer, trans, eps[0]),
+         sac_losses.critic_loss(ts.q_layers, ts.policy_layers, normalizer, ts.target_q_layers, alpha,
+                                trans, eps[1], scaling, discounting),
+         sac_losses.actor_loss(ts.policy_layers, normalizer, ts.q_layers, alpha, trans, eps[2]))
+  assert sac_losses.target_entropy(2) == -1.0
+  for name, g_, w in zip(('alpha', 'critic', 'actor'), got, want):
+    g_ = g_.detach()
+    print(f'{name}_loss: got {float(g_)!r} want {float(w)!r} rel {abs(float(g_) - w) / abs(w):.2e}')
+    assert g_.dtype == torch.float64
+    # a few hundred float64 roundings; any formula error is many orders larger
+    assert abs(float(g_) - w) <= 1e-12 * abs(w), name
+  # what each loss differentiates: alpha_loss log_alpha alone (the entropy
+  # term is held), critic_loss the q network alone (the target is held)
+  assert torch.autograd.grad(got[0], sac_networks.q_parameters([ts.policy_layers]),
+                             allow_unused=True, retain_graph=True)[0] is None
+  assert float(torch.autograd.grad(got[0], ts.log_alpha)[0]) != 0
+  assert all(g_ is None for g_ in torch.autograd.grad(
+      got[1], sac_networks.q_parameters([ts.policy_layers]), allow_unused=True, retain_graph=True))
+  # the truncated row carries no q error: its reward does not matter
+  trans2 = dict(trans, reward=trans['reward'].clone())
+  trans2['reward'][0] += 100.0
+  again = sac_losses.critic_loss(ts.q_layers, ts.policy_layers, normalizer, ts.target_q_layers, alpha,
+                                 trans2, eps[1], scaling, discounting)
+  assert float(again) == float(got[1])
+
+
+# ---- sgd_step ---------------------------------------------------------------------------------
+
+def _adam_first_step(p, g, lr):
+  """The first Adam step from zero moments: m / (1 - b1) = g, sqrt(v / (1 -
+  b2)) = |g|, so p - lr * g / (|g| + eps)."""
+  return p - lr * g / (np.abs(g) + 1e-8)
+
+
+def test_sgd_step_keeps_the_references_ordering():
+  lr, tau, scaling, discounting = 1e-2, 0.25, 0.5, 0.9
+  ts, normalizer, trans, eps = _case(learning_rate=lr)
+  old = _np_state(ts)
+  norm_np = (_n(normalizer[0]), _n(normalizer[1]))
+  tr, ep = _np_trans(trans), [_n(e) for e in eps]
+  losses = lambda s: _reference_losses(s['log_alpha'], s['policy'], s['q'], s['target_q'], norm_np,  # noqa: E731
+                                       tr, ep, scaling, discounting, 2)
+  # the gradients at the old state, from the losses the previous test pinned
+  alpha_old = torch.exp(ts.log_alpha.detach())
+  g_alpha = torch.autograd.grad(sac_losses.alpha_loss(ts.log_alpha, ts.policy_layers, normalizer,
+                                                      trans, eps[0]), ts.log_alpha)[0]
+  q_params = sac_networks.q_parameters(ts.q_layers)
+  g_q = torch.autograd.grad(sac_losses.critic_loss(
+      ts.q_layers, ts.policy_layers, normalizer, ts.target_q_layers, alpha_old, trans, eps[1],
+      scaling, discounting), q_params)
+  p_params = sac_networks.q_parameters([ts.policy_layers])
+  g_p = torch.autograd.grad(sac_losses.actor_loss(ts.policy_layers, normalizer, ts.q_layers,
+                                                  alpha_old, trans, eps[2]), p_params)
+  want_log_alpha = _adam_first_step(old['log_alpha'], float(g_alpha), 3e-4)
+  want_q = [_adam_first_step(_n(p), _n(g), lr) for p, g in zip(q_params, g_q)]
+  want_p = [_adam_first_step(_n(p), _n(g), lr) for p, g in zip(p_params, g_p)]
+  target_old = [_n(t) for t in sac_networks.q_parameters(ts.target_q_layers)]
+
+  metrics = sac.sgd_step(ts, normalizer, trans, eps, reward_scaling=scaling,
+                         discounting=discounting, tau=tau)
+  assert sorted(metrics) == ['actor_loss', 'alpha', 'alpha_loss', 'critic_loss']
+  assert ts.gradient_steps == 1
+  new = _np_state(ts)
+  # every loss is the old state's
+  a_old, c_old, p_old = losses(old)
+  for k, w in (('alpha_loss', a_old), ('critic_loss', c_old), ('actor_loss', p_old)):
+    assert abs(float(metrics[k]) - w) <= 1e-12 * abs(w), k
+  # and a misplaced new value would show: the new alpha or the new policy in
+  # the critic loss, the new alpha or the new q parameters in the actor loss
+  wrong = {
+      'critic, new alpha': (losses(dict(old, log_alpha=new['log_alpha']))[1], c_old),
+      'critic, new policy': (losses(dict(old, policy=new['policy']))[1], c_old),
+      'actor, new alpha': (losses(dict(old, log_alpha=new['log_alpha']))[2], p_old),
+      'actor, new q': (losses(dict(old, q=new['q']))[2], p_old),
+      'alpha, new policy': (losses(dict(old, policy=new['policy']))[0], a_old),
+  }
+  for name, (w, right) in wrong.items():
+    print(f'{name}: {w!r} against {right!r}')
+    assert abs(w - right) > 1e-7 * abs(right), name
+  # the three Adam steps: alpha at 3e-4, the networks at learning_rate
+  assert abs(new['log_alpha'] - want_log_alpha) <= 1e-12
+  assert abs(abs(new['log_alpha'] - old['log_alpha']) - 3e-4) < 1e-9
+  for got, w in zip(sac_networks.q_parameters(ts.q_layers) + sac_networks.q_parameters([ts.policy_layers]),
+                    want_q + want_p):
+    np.testing.assert_allclose(_n(got), w, rtol=0, atol=1e-12)
+  moved = np.abs(_n(q_params[0]) - old['q'][0][0][0])
+  assert abs(moved.max() - lr) < 1e-6
+  # the metric alpha is exp of the NEW log_alpha
+  assert float(metrics['alpha']) == float(np.exp(new['log_alpha'])) != float(np.exp(old['log_alpha']))
+  # the target moves towards the NEW q parameters
+  for t_new, t_old, q_new in zip(sac_networks.q_parameters(ts.target_q_layers), target_old,
+                                 sac_networks.q_parameters(ts.q_layers)):
+    assert np.array_equal(_n(t_new), t_old * (1 - tau) + _n(q_new) * tau)
+
+
+def test_target_update_is_exact_on_dyadic_values():
+  ts, normalizer, trans, eps = _case(learning_rate=0.0)  # q stays where it is
+  with torch.no_grad():
+    for k, (t, q) in enumerate(zip(sac_networks.q_parameters(ts.target_q_layers),
+                                   sac_networks.q_parameters(ts.q_layers))):
+      t.fill_(1.0 + k)
+      q.fill_(3.0 + 5 * k)
+  for step in (1, 2):
+    sac.sgd_step(ts, normalizer, trans, eps, tau=0.25)
+    for k, (t, q) in enumerate(zip(sac_networks.q_parameters(ts.target_q_layers),
+                                   sac_networks.q_parameters(ts.q_layers))):
+      assert float(q.detach().flatten()[0]) == 3.0 + 5 * k
+      want = 1.0 + k
+      for _ in range(step):
+        want = want * 0.75 + (3.0 + 5 * k) * 0.25  # exact: multiples of 1 / 16
+      assert torch.equal(t, torch.full_like(t, want)), (step, k)
+
+
+def test_networks():
+  policy, q = sac_networks.make_sac_networks(7, 3)
+  assert [tuple(w.shape) for w, _ in policy] == [(7, 256), (256, 256), (256, 6)]
+  assert len(q) == 2
+  for c in q:
+    assert [tuple(w.shape) for w, _ in c] == [(10, 256), (256, 256), (256, 1)]
+  assert not torch.equal(q[0][0][0], q[1][0][0])
+  for w, b in policy + q[0] + q[1]:
+    assert w.requires_grad and b.requires_grad and float(b.detach().abs().max()) == 0
+    lim = (3.0 / w.shape[0]) ** 0.5  # lecun uniform
+    assert 0.8 * lim < float(w.detach().abs().max()) <= lim
+  out = sac_networks.q_apply(q, torch.zeros(4, 7), torch.zeros(4, 3))
+  assert tuple(out.shape) == (4, 2)
+  # relu, not PPO's swish: a negative pre-activation passes nothing on
+  one = [(torch.tensor([[-1.0]]), torch.zeros(1)), (torch.ones(1, 1), torch.zeros(1))]
+  assert float(sac_networks.q_apply([one], torch.ones(1, 1), torch.zeros(1, 0))) == 0.0
+
+
+# ---- train ------------------------------------------------------------------------------------
+
+def test_step_accounting_and_argument_checks():
+  # 2,000 steps, 8 envs, 100 rows of prefill: ceil(100 / 8) = 13 actor steps = 104 env steps;
+  # two epochs of ceil(1896 / (2 * 8)) = 119 training steps
+  a = sac.step_accounting(num_timesteps=2000, num_evals=3, min_replay_size=100, num_envs=8,
+                          action_repeat=1)
+  assert (a.env_steps_per_actor_step, a.num_prefill_actor_steps, a.num_prefill_env_steps) == (8, 13, 104)
+  assert (a.num_evals_after_init, a.num_training_steps_per_epoch) == (2, 119)
+  assert a.max_replay_size == 2000  # the default: num_timesteps
+  assert 104 + 2 * 119 * 8 >= 2000
+  # action_repeat multiplies the env steps of an actor step, not the rows it inserts
+  b = sac.step_accounting(10_000, 1, 1000, 64, 2, max_replay_size=4096)
+  assert (b.env_steps_per_actor_step, b.num_prefill_actor_steps, b.num_prefill_env_steps) == (128, 16, 2048)
+  assert (b.num_evals_after_init, b.num_training_steps_per_epoch) == (1, 63)  # ceil(7952 / 128)
+  assert b.max_replay_size == 4096
+  c = sac.step_accounting(100, 2, 0, 1, 1)
+  assert (c.num_prefill_actor_steps, c.num_training_steps_per_epoch) == (0, 100)
+  for bad in (2000, 2001):
+    with pytest.raises(ValueError, match='min_replay_size >= num_timesteps'):
+      sac.step_accounting(2000, 3, bad, 8, 1)
+  # before any env or device is touched
+  with pytest.raises(ValueError, match='min_replay_size >= num_timesteps'):
+    sac.train('inverted_pendulum', num_timesteps=100, episode_length=10, min_replay_size=100,
+              device='cuda:0')
+  with pytest.raises(NotImplementedError):
+    sac.train('inverted_pendulum', num_timesteps=100, episode_length=10, checkpoint_logdir='x',
+              device='cuda:0')
+  # the reference's argument names and defaults
+  sig = inspect.signature(sac.train).parameters
+  want = dict(action_repeat=1, num_envs=1, num_eval_envs=128, learning_rate=1e-4, discounting=0.9,
+              seed=0, batch_size=256, num_evals=1, normalize_observations=False,
+              max_devices_per_host=None, reward_scaling=1.0, tau=0.005, min_replay_size=0,
+              max_replay_size=None, grad_updates_per_step=1, deterministic_eval=False,
+              checkpoint_logdir=None, eval_env=None, device=None)
+  for k, v in want.items():
+    assert sig[k].default == v, k
+  assert list(sig)[:3] == ['environment', 'num_timesteps', 'episode_length'] and 'progress_fn' in sig
+  assert sig['network_factory'].default is sac_networks.make_sac_networks
+  from brax_amd import training
+  assert training.sac is sac
