@@ -98,6 +98,9 @@ _SIGS = {
     'bx_population_delta': abi.SIGNATURES['bx_population_delta'],
     'bx_replay_insert': abi.SIGNATURES['bx_replay_insert'],
     'bx_replay_sample': abi.SIGNATURES['bx_replay_sample'],
+    'bx_mlp_sizes': abi.SIGNATURES['bx_mlp_sizes'],
+    'bx_mlp_forward': abi.SIGNATURES['bx_mlp_forward'],
+    'bx_mlp_backward': abi.SIGNATURES['bx_mlp_backward'],
 }
 
 EXPORTS = tuple(_SIGS)

@@ -180,6 +180,32 @@ REPLAY_SAMPLE_ARGS = (
     ('data', _vp), ('capacity', C.c_int64), ('row_words', C.c_int64), ('position', C.c_int64),
     ('size', C.c_int64), ('n_samples', C.c_int64), ('seed', C.c_uint64), ('offset', C.c_uint64),
     ('dst', _fields), ('idx_out', _vp), ('stream', _vp))
+MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_IN = 8, 256, 1024  # BX_MLP_MAX_*
+
+
+class BxMlp(C.Structure):
+  """One MLP for bx_mlp_forward / bx_mlp_backward: w[l] is (in[l], out[l])
+  row-major float32, b[l] is (out[l],); the activation is a
+  POLICY_ACTIVATIONS code."""
+  _fields_ = [('n_layers', C.c_int32), ('activation', C.c_int32),
+              ('in', C.c_int32 * MLP_MAX_LAYERS), ('out', C.c_int32 * MLP_MAX_LAYERS),
+              ('w', C.c_void_p * MLP_MAX_LAYERS), ('b', C.c_void_p * MLP_MAX_LAYERS)]
+
+
+class BxMlpGrads(C.Structure):
+  """Where bx_mlp_backward writes each layer's gradients; None switches one off."""
+  _fields_ = [('dw', C.c_void_p * MLP_MAX_LAYERS), ('db', C.c_void_p * MLP_MAX_LAYERS)]
+
+
+_mlp = C.POINTER(BxMlp)
+MLP_SIZES_ARGS = (('mlp_bytes', C.POINTER(C.c_int32)), ('grads_bytes', C.POINTER(C.c_int32)))
+MLP_FORWARD_ARGS = (
+    ('net', _mlp), ('rows', C.c_int64), ('x', _vp), ('x_stride', C.c_int64), ('y', _vp),
+    ('saved', _vp), ('stream', _vp))
+MLP_BACKWARD_ARGS = (
+    ('net', _mlp), ('rows', C.c_int64), ('x', _vp), ('x_stride', C.c_int64), ('saved', _vp),
+    ('dy', _vp), ('dx', _vp), ('grads', C.POINTER(BxMlpGrads)), ('workspace', _vp),
+    ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
 PLAN_FIELDS = ('mode', 'lanes', 'lds_bytes', 'feat', 'gw', 'fold', 'jb', 'cb')  # bx_system_blob
 SYSTEM_BLOB_ARGS = (
     ('desc', _vp), ('reset', _vp), ('words', C.POINTER(C.c_uint32)), ('capacity', C.c_int64),
@@ -189,7 +215,9 @@ ARGS = {'bx_system_blob': SYSTEM_BLOB_ARGS,
         'bx_env_eval_population': EVAL_POPULATION_ARGS, 'bx_compute_gae': COMPUTE_GAE_ARGS,
         'bx_population_perturb': POPULATION_PERTURB_ARGS,
         'bx_population_delta': POPULATION_DELTA_ARGS,
-        'bx_replay_insert': REPLAY_INSERT_ARGS, 'bx_replay_sample': REPLAY_SAMPLE_ARGS}
+        'bx_replay_insert': REPLAY_INSERT_ARGS, 'bx_replay_sample': REPLAY_SAMPLE_ARGS,
+        'bx_mlp_sizes': MLP_SIZES_ARGS, 'bx_mlp_forward': MLP_FORWARD_ARGS,
+        'bx_mlp_backward': MLP_BACKWARD_ARGS}
 SIGNATURES = {name: ([t for _, t in args], C.c_int) for name, args in ARGS.items()}
 
 

@@ -10,6 +10,7 @@
 
 #include "../../include/brax_amd.h"
 #include "bx_blob.h"
+#include "mlp_launch.h"
 #include "pbd_features.h"
 #include "pbd_launch.h"
 #include "pbd_layout.h"
@@ -1182,6 +1183,108 @@ int bx_replay_sample(const float* data, int64_t capacity, int64_t row_words, int
   DeviceScope scope(dev);
   if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
   HIP_OK(launch_replay_sample(a, st));
+  return 0;
+}
+
+namespace {
+
+// the checks bx_mlp_forward and bx_mlp_backward share, and the kernels' form
+// of the network (the hidden layers' column offsets in `saved` and `dz`)
+int mlp_args(const bx_mlp* net, int64_t rows, int64_t x_stride, MlpNet* m) {
+  if (!net) return fail("null argument");
+  if (net->n_layers < 1 || net->n_layers > BX_MLP_MAX_LAYERS)
+    return fail("n_layers " + std::to_string(net->n_layers) + " outside 1.." +
+                std::to_string(BX_MLP_MAX_LAYERS));
+  if (net->activation != BX_POLICY_SWISH && net->activation != BX_POLICY_RELU &&
+      net->activation != BX_POLICY_TANH)
+    return fail("unknown activation " + std::to_string(net->activation));
+  if (rows < 0) return fail("negative rows");
+  if (rows > ((int64_t)1 << 31)) return fail("too many rows for one launch");
+  m->n_layers = net->n_layers;
+  m->activation = net->activation;
+  int hidden = 0;
+  for (int l = 0; l < net->n_layers; ++l) {
+    const int in = net->in[l], out = net->out[l];
+    if (out < 1 || out > BX_MLP_MAX_WIDTH)
+      return fail("layer " + std::to_string(l) + ": width " + std::to_string(out) +
+                  " outside 1.." + std::to_string(BX_MLP_MAX_WIDTH));
+    if (l == 0 && (in < 1 || in > BX_MLP_MAX_IN))
+      return fail("input width " + std::to_string(in) + " outside 1.." +
+                  std::to_string(BX_MLP_MAX_IN));
+    if (l > 0 && in != net->out[l - 1])
+      return fail("layer " + std::to_string(l) + ": in " + std::to_string(in) +
+                  " != the previous out " + std::to_string(net->out[l - 1]));
+    if (!net->w[l] || !net->b[l]) return fail("null weight or bias");
+    m->in[l] = in;
+    m->out[l] = out;
+    m->w[l] = net->w[l];
+    m->b[l] = net->b[l];
+    m->off[l] = hidden;
+    if (l + 1 < net->n_layers) hidden += out;
+  }
+  m->hidden = hidden;
+  if (x_stride < net->in[0])
+    return fail("x_stride " + std::to_string(x_stride) + " below the input width " +
+                std::to_string(net->in[0]));
+  return 0;
+}
+
+}  // namespace
+
+int bx_mlp_sizes(int32_t* mlp_bytes, int32_t* grads_bytes) {
+  if (!mlp_bytes || !grads_bytes) return fail("null argument");
+  *mlp_bytes = (int32_t)sizeof(bx_mlp);
+  *grads_bytes = (int32_t)sizeof(bx_mlp_grads);
+  return 0;
+}
+
+int bx_mlp_forward(const bx_mlp* net, int64_t rows, const float* x, int64_t x_stride, float* y,
+                   float* saved, void* stream) {
+  MlpNet m{};
+  if (mlp_args(net, rows, x_stride, &m)) return 1;
+  if (rows == 0) return 0;
+  if (!x || !y) return fail("null argument");
+  int dev = -1;
+  hipStream_t st = as_stream(stream);
+  if (st) HIP_OK(hipStreamGetDevice(st, &dev));
+  else HIP_OK(hipGetDevice(&dev));
+  DeviceScope scope(dev);
+  if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
+  HIP_OK(launch_mlp_forward(m, rows, x, x_stride, y, saved, st));
+  return 0;
+}
+
+int bx_mlp_backward(const bx_mlp* net, int64_t rows, const float* x, int64_t x_stride,
+                    const float* saved, const float* dy, float* dx, const bx_mlp_grads* grads,
+                    void* workspace, int64_t* workspace_bytes, void* stream) {
+  if (!workspace_bytes) return fail("null argument");
+  MlpNet m{};
+  if (mlp_args(net, rows, x_stride, &m)) return 1;
+  const int64_t need = std::max<int64_t>(16, 4 * rows * (int64_t)m.hidden);
+  if (!workspace) {  // the size query
+    *workspace_bytes = need;
+    return 0;
+  }
+  if (rows == 0) return 0;
+  if (!x || !dy) return fail("null argument");
+  if (m.n_layers > 1 && !saved) return fail("null saved with hidden layers");
+  if (*workspace_bytes < need)
+    return fail("workspace of " + std::to_string(*workspace_bytes) + " bytes, " +
+                std::to_string(need) + " needed");
+  if ((uintptr_t)workspace & 15) return fail("workspace not 16-byte aligned");
+  MlpGrads g{};
+  if (grads)
+    for (int l = 0; l < m.n_layers; ++l) {
+      g.dw[l] = grads->dw[l];
+      g.db[l] = grads->db[l];
+    }
+  int dev = -1;
+  hipStream_t st = as_stream(stream);
+  if (st) HIP_OK(hipStreamGetDevice(st, &dev));
+  else HIP_OK(hipGetDevice(&dev));
+  DeviceScope scope(dev);
+  if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
+  HIP_OK(launch_mlp_backward(m, g, rows, x, x_stride, saved, dy, dx, (float*)workspace, st));
   return 0;
 }
 

@@ -14,4 +14,6 @@ from brax_amd.training.losses import Transition, ppo_loss
 from brax_amd.training.networks import make_ppo_networks, mlp
 from brax_amd.training.replay_buffers import UniformSamplingQueue, transition_fields
 from brax_amd.training.sac_networks import make_sac_networks
+# (the module, not its function of the same name: `training.fused_mlp.fused_mlp`)
+from brax_amd.training import fused_mlp
 from brax_amd.training.ppo import Learner, RunningStatistics, step_accounting, train, transitions

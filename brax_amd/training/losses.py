@@ -65,7 +65,8 @@ def ppo_loss(policy_layers: Layers, value_layers: Layers, normalizer, data: Tran
              entropy_cost: float = 1e-4, discounting: float = 0.9, reward_scaling: float = 1.0,
              gae_lambda: float = 0.95, clipping_epsilon: float = 0.3,
              normalize_advantage: bool = True, activation: str = 'swish', min_std: float = 1e-3,
-             fused: Optional[bool] = None) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+             fused: Optional[bool] = None,
+             fused_mlp=False) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
   """`(loss, metrics)` of one minibatch.
 
   Args:
@@ -75,14 +76,15 @@ def ppo_loss(policy_layers: Layers, value_layers: Layers, normalizer, data: Tran
     eps: `(B, T, A)` standard-normal draws for the entropy term's sample (the
       reference's `rng`, explicit).
     fused: passed to `compute_gae`.
+    fused_mlp: `networks.mlp`'s `fused` for the three network evaluations.
   """
   data = data.map(lambda x: x.transpose(0, 1))  # time first
   eps = eps.transpose(0, 1)
   obs = normalize(data.observation, normalizer)
-  logits = mlp(policy_layers, obs, activation)
-  baseline = mlp(value_layers, obs, activation).squeeze(-1)
+  logits = mlp(policy_layers, obs, activation, fused_mlp)
+  baseline = mlp(value_layers, obs, activation, fused_mlp).squeeze(-1)
   bootstrap_value = mlp(value_layers, normalize(data.next_observation[-1], normalizer),
-                        activation).squeeze(-1)
+                        activation, fused_mlp).squeeze(-1)
   loc, s = torch.chunk(logits, 2, dim=-1)
   scale = head_scale(s, min_std)
   target_log_probs = normal_tanh_log_prob(loc, scale, data.raw_action).sum(-1)

@@ -44,9 +44,14 @@ def make_ppo_networks(observation_size: int, action_size: int,
   return policy, value
 
 
-def mlp(layers: Layers, x: torch.Tensor, activation: str = 'swish') -> torch.Tensor:
+def mlp(layers: Layers, x: torch.Tensor, activation: str = 'swish', fused=False) -> torch.Tensor:
   """`networks.MLP.__call__`: the activation after every layer but the last
-  (`MLPPolicy.forward`'s loop)."""
+  (`MLPPolicy.forward`'s loop). `fused` other than False goes through
+  `fused_mlp.fused_mlp` (True: the kernels or NotImplementedError; None: the
+  kernels where they apply, else the loop below)."""
+  if fused is not False:
+    from brax_amd.training.fused_mlp import fused_mlp  # pylint: disable=import-outside-toplevel
+    return fused_mlp(layers, x, activation, fused)
   fn = _ACTIVATIONS[activation]
   for k, (w, b) in enumerate(layers):
     x = x @ w + b

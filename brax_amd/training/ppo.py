@@ -115,7 +115,7 @@ class Learner:
                clipping_epsilon: float = 0.3, gae_lambda: float = 0.95,
                normalize_observations: bool = False, normalize_advantage: bool = True,
                seed: int = 0, network_factory=ppo_networks.make_ppo_networks, device=None,
-               fused_gae: Optional[bool] = None, action_repeat: int = 1):
+               fused_gae: Optional[bool] = None, action_repeat: int = 1, fused_mlp=False):
     assert batch_size * num_minibatches % num_envs == 0
     self.env, self.device = env, torch.device(device)
     self.action_repeat = int(action_repeat)
@@ -123,7 +123,7 @@ class Learner:
     self.batch_size, self.num_minibatches = int(batch_size), int(num_minibatches)
     self.num_updates_per_batch = int(num_updates_per_batch)
     self.unrolls = batch_size * num_minibatches // num_envs
-    self.seed, self.fused_gae = int(seed), fused_gae
+    self.seed, self.fused_gae, self.fused_mlp = int(seed), fused_gae, fused_mlp
     self.loss_kwargs = dict(entropy_cost=entropy_cost, discounting=discounting,
                             reward_scaling=reward_scaling, gae_lambda=gae_lambda,
                             clipping_epsilon=clipping_epsilon,
@@ -201,7 +201,8 @@ class Learner:
         mb = shuffled.map(lambda x, m=m: x[m * bs:(m + 1) * bs])
         eps = torch.randn((bs, self.unroll_length, A), generator=self._gen, device=self.device)
         loss, metrics = ppo_loss(self.policy_layers, self.value_layers, self._mean_std, mb, eps,
-                                 fused=self.fused_gae, **self.loss_kwargs)
+                                 fused=self.fused_gae, fused_mlp=self.fused_mlp,
+                                 **self.loss_kwargs)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.optimizer.step()
@@ -229,7 +230,7 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
           deterministic_eval: bool = False, network_factory=ppo_networks.make_ppo_networks,
           progress_fn: Callable[[int, dict], None] = lambda *args: None,
           normalize_advantage: bool = True, eval_env=None, device=None,
-          fused_gae: Optional[bool] = None):
+          fused_gae: Optional[bool] = None, fused_mlp=False):
   """PPO training; the reference's arguments and defaults
   (`ppo/train.py:61-86`).
 
@@ -241,6 +242,9 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
       `num_eval_envs` (a name is created at both sizes).
     device: the GPU (default `cuda`).
     fused_gae: `compute_gae`'s `fused` (None: the kernel).
+    fused_mlp: the loss's networks through `fused_mlp.fused_mlp` (False: chained
+      torch; True: the kernels or NotImplementedError; None: the kernels where
+      they apply).
   Returns:
     `(make_policy, params, metrics)`: `make_policy(params, deterministic=False)`
     gives an `MLPPolicy`; `params` is (the normaliser or None, the policy
@@ -269,7 +273,7 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
                     normalize_observations=normalize_observations,
                     normalize_advantage=normalize_advantage, seed=seed,
                     network_factory=network_factory, device=dev, fused_gae=fused_gae,
-                    action_repeat=action_repeat)
+                    action_repeat=action_repeat, fused_mlp=fused_mlp)
   key = np.array([0, int(seed)], np.uint32)  # jax.random.PRNGKey(seed) layout
   key_env, key_eval = wrappers.split_key(key)
   learner.reset(key_env)

@@ -108,7 +108,7 @@ def _apply(optimizer, params, grads):
 
 def sgd_step(ts: TrainingState, normalizer, transitions: Mapping[str, torch.Tensor],
              eps: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], reward_scaling: float = 1.0,
-             discounting: float = 0.9, tau: float = 0.005):
+             discounting: float = 0.9, tau: float = 0.005, fused_mlp=False):
   """One gradient step in the reference's order (`train.py:214-269`).
 
   The alpha update comes first, but the critic and actor losses read `exp` of
@@ -123,18 +123,21 @@ def sgd_step(ts: TrainingState, normalizer, transitions: Mapping[str, torch.Tens
     normalizer: `(mean, std)` or None.
     eps: the standard-normal draws `(B, A)` of the alpha, critic and actor
       losses' samples (the reference's three keys).
+    fused_mlp: the losses' `fused_mlp` (`networks.mlp`'s `fused`).
   Returns:
     the metrics (detached tensors): critic_loss, actor_loss, alpha_loss, alpha.
   """
   eps_alpha, eps_critic, eps_actor = eps
   policy_params = parameters(ts.policy_layers)
   q_params = sac_networks.q_parameters(ts.q_layers)
-  a_loss = sac_losses.alpha_loss(ts.log_alpha, ts.policy_layers, normalizer, transitions, eps_alpha)
+  a_loss = sac_losses.alpha_loss(ts.log_alpha, ts.policy_layers, normalizer, transitions, eps_alpha,
+                                 fused_mlp)
   alpha = torch.exp(ts.log_alpha.detach())
   c_loss = sac_losses.critic_loss(ts.q_layers, ts.policy_layers, normalizer, ts.target_q_layers,
-                                  alpha, transitions, eps_critic, reward_scaling, discounting)
+                                  alpha, transitions, eps_critic, reward_scaling, discounting,
+                                  fused_mlp)
   p_loss = sac_losses.actor_loss(ts.policy_layers, normalizer, ts.q_layers, alpha, transitions,
-                                 eps_actor)
+                                 eps_actor, fused_mlp)
   a_grads = torch.autograd.grad(a_loss, [ts.log_alpha])
   c_grads = torch.autograd.grad(c_loss, q_params)
   p_grads = torch.autograd.grad(p_loss, policy_params)
@@ -163,12 +166,12 @@ class Learner:
                learning_rate: float = 1e-4, discounting: float = 0.9, reward_scaling: float = 1.0,
                tau: float = 0.005, normalize_observations: bool = False, seed: int = 0,
                network_factory=sac_networks.make_sac_networks, device=None,
-               action_repeat: int = 1, fused_buffer: Optional[bool] = None):
+               action_repeat: int = 1, fused_buffer: Optional[bool] = None, fused_mlp=False):
     self.env, self.device = env, torch.device(device)
     self.num_envs, self.action_repeat = int(num_envs), int(action_repeat)
     self.batch_size, self.grad_updates_per_step = int(batch_size), int(grad_updates_per_step)
     self.num_prefill_actor_steps = int(num_prefill_actor_steps)
-    self.seed, self.fused_buffer = int(seed), fused_buffer
+    self.seed, self.fused_buffer, self.fused_mlp = int(seed), fused_buffer, fused_mlp
     self.loss_kwargs = dict(reward_scaling=reward_scaling, discounting=discounting, tau=tau)
     O, A = env.observation_size, env.action_size
     self.ts = init_training_state(O, A, learning_rate, network_factory, seed, self.device)
@@ -238,7 +241,8 @@ class Learner:
       mb = {k: v[g * self.batch_size:(g + 1) * self.batch_size] for k, v in transitions.items()}
       eps = tuple(torch.randn((self.batch_size, A), generator=self._gen, device=self.device)
                   for _ in range(3))
-      for k, v in sgd_step(self.ts, self._mean_std, mb, eps, **self.loss_kwargs).items():
+      for k, v in sgd_step(self.ts, self._mean_std, mb, eps, fused_mlp=self.fused_mlp,
+                           **self.loss_kwargs).items():
         sums[k] = v + sums.get(k, 0)
     self.actor.load_(_detached(self.ts.policy_layers))
     return {k: v / self.grad_updates_per_step for k, v in sums.items()}
@@ -261,7 +265,7 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
           deterministic_eval: bool = False, network_factory=sac_networks.make_sac_networks,
           progress_fn: Callable[[int, dict], None] = lambda *args: None,
           checkpoint_logdir: Optional[str] = None, eval_env=None, device=None,
-          fused_buffer: Optional[bool] = None):
+          fused_buffer: Optional[bool] = None, fused_mlp=False):
   """SAC training; the reference's arguments and defaults
   (`sac/train.py:106-129`).
 
@@ -279,6 +283,9 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
       `num_eval_envs` (a name is created at both sizes).
     device: the GPU (default `cuda`).
     fused_buffer: the queue's `fused` (None: the kernels).
+    fused_mlp: the losses' networks through `fused_mlp.fused_mlp` (False: chained
+      torch; True: the kernels or NotImplementedError; None: the kernels where
+      they apply).
   Returns:
     `(make_policy, params, metrics)`: `make_policy(params, deterministic=False)`
     gives an `MLPPolicy`; `params` is (the normaliser or None, the policy
@@ -311,7 +318,7 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
                     reward_scaling=reward_scaling, tau=tau,
                     normalize_observations=normalize_observations, seed=seed,
                     network_factory=network_factory, device=dev, action_repeat=action_repeat,
-                    fused_buffer=fused_buffer)
+                    fused_buffer=fused_buffer, fused_mlp=fused_mlp)
   key = np.array([0, int(seed)], np.uint32)  # jax.random.PRNGKey(seed) layout
   key_env, key_eval = wrappers.split_key(key)
   learner.reset(key_env)

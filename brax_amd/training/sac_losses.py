@@ -27,19 +27,21 @@ def _scalar(t):
   return t.reshape(t.shape[0])
 
 
-def _sample(policy_layers, obs, eps):
+def _sample(policy_layers, obs, eps, fused_mlp=False):
   """`sample_no_postprocessing` and `log_prob` of it: (raw action, log_prob)."""
-  loc, s = torch.chunk(mlp(policy_layers, obs, ACTIVATION), 2, dim=-1)
+  loc, s = torch.chunk(mlp(policy_layers, obs, ACTIVATION, fused_mlp), 2, dim=-1)
   scale = head_scale(s, MIN_STD)
   raw = loc + scale * eps.to(loc.dtype)
   return raw, normal_tanh_log_prob(loc, scale, raw).sum(-1)
 
 
 def alpha_loss(log_alpha: torch.Tensor, policy_layers: Layers, normalizer,
-               transitions: Mapping[str, torch.Tensor], eps: torch.Tensor) -> torch.Tensor:
+               transitions: Mapping[str, torch.Tensor], eps: torch.Tensor,
+               fused_mlp=False) -> torch.Tensor:
   """Eq 18 of arXiv:1812.05905 (`losses.py:40-51`); differentiable in `log_alpha`."""
   action_size = eps.shape[-1]
-  _, log_prob = _sample(policy_layers, normalize(transitions['observation'], normalizer), eps)
+  _, log_prob = _sample(policy_layers, normalize(transitions['observation'], normalizer), eps,
+                        fused_mlp)
   alpha = torch.exp(log_alpha)
   loss = alpha * (-log_prob - target_entropy(action_size)).detach()
   return torch.mean(loss)
@@ -48,14 +50,15 @@ def alpha_loss(log_alpha: torch.Tensor, policy_layers: Layers, normalizer,
 def critic_loss(q_layers: List[Layers], policy_layers: Layers, normalizer,
                 target_q_layers: List[Layers], alpha: torch.Tensor,
                 transitions: Mapping[str, torch.Tensor], eps: torch.Tensor,
-                reward_scaling: float = 1.0, discounting: float = 0.9) -> torch.Tensor:
+                reward_scaling: float = 1.0, discounting: float = 0.9,
+                fused_mlp=False) -> torch.Tensor:
   """`losses.py:53-79`; differentiable in `q_layers` (the target is held)."""
   obs = normalize(transitions['observation'], normalizer)
   next_obs = normalize(transitions['next_observation'], normalizer)
-  q_old_action = q_apply(q_layers, obs, transitions['action'])
-  next_raw, next_log_prob = _sample(policy_layers, next_obs, eps)
+  q_old_action = q_apply(q_layers, obs, transitions['action'], fused_mlp)
+  next_raw, next_log_prob = _sample(policy_layers, next_obs, eps, fused_mlp)
   next_action = torch.tanh(next_raw)
-  next_q = q_apply(target_q_layers, next_obs, next_action)
+  next_q = q_apply(target_q_layers, next_obs, next_action, fused_mlp)
   next_v = torch.min(next_q, dim=-1).values - alpha * next_log_prob
   target_q = (_scalar(transitions['reward']) * reward_scaling
               + _scalar(transitions['discount']) * discounting * next_v).detach()
@@ -66,11 +69,12 @@ def critic_loss(q_layers: List[Layers], policy_layers: Layers, normalizer,
 
 
 def actor_loss(policy_layers: Layers, normalizer, q_layers: List[Layers], alpha: torch.Tensor,
-               transitions: Mapping[str, torch.Tensor], eps: torch.Tensor) -> torch.Tensor:
+               transitions: Mapping[str, torch.Tensor], eps: torch.Tensor,
+               fused_mlp=False) -> torch.Tensor:
   """`losses.py:81-94`; differentiable in `policy_layers`."""
   obs = normalize(transitions['observation'], normalizer)
-  raw, log_prob = _sample(policy_layers, obs, eps)
+  raw, log_prob = _sample(policy_layers, obs, eps, fused_mlp)
   action = torch.tanh(raw)
-  q_action = q_apply(q_layers, obs, action)
+  q_action = q_apply(q_layers, obs, action, fused_mlp)
   min_q = torch.min(q_action, dim=-1).values
   return torch.mean(alpha * log_prob - min_q)

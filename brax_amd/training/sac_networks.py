@@ -27,10 +27,11 @@ def make_sac_networks(observation_size: int, action_size: int,
   return policy, q
 
 
-def q_apply(q_layers: List[Layers], obs: torch.Tensor, action: torch.Tensor) -> torch.Tensor:
+def q_apply(q_layers: List[Layers], obs: torch.Tensor, action: torch.Tensor,
+            fused_mlp=False) -> torch.Tensor:
   """`QModule.__call__` on observations that are already normalised: (B, n_critics)."""
   hidden = torch.cat([obs, action], dim=-1)
-  return torch.cat([mlp(c, hidden, ACTIVATION) for c in q_layers], dim=-1)
+  return torch.cat([mlp(c, hidden, ACTIVATION, fused_mlp) for c in q_layers], dim=-1)
 
 
 def q_parameters(q_layers: List[Layers]) -> List[torch.Tensor]:

@@ -802,6 +802,75 @@ int bx_replay_sample(const float* data, int64_t capacity, int64_t row_words, int
                      int64_t size, int64_t n_samples, uint64_t seed, uint64_t offset,
                      const bx_fields* dst, int64_t* idx_out, void* stream);
 
+/* The learners' MLPs (the reference's `networks.MLP`): y = layer_{L-1}(...
+ * act(layer_0(x))), layer_l(a) = a . w[l] + b[l], the activation (BX_POLICY_SWISH
+ * / RELU / TANH) after every layer but the last. float32; w[l] is (in[l],
+ * out[l]) row-major and b[l] is (out[l],), separate device arrays that the
+ * kernels only read (an optimiser updates them in place between calls);
+ * n_layers 1 .. BX_MLP_MAX_LAYERS, every out[l] 1 .. BX_MLP_MAX_WIDTH, in[0]
+ * 1 .. BX_MLP_MAX_IN, in[l] = out[l - 1]. Every product is an f32 MFMA, a
+ * k-ordered fmaf chain; NaN and Inf propagate as IEEE has them and a
+ * non-finite input row reaches no other row's y or dx. No system handle: the
+ * launches go to the device that owns `stream` (the current device for NULL).
+ * (Additive: no ABI bump.) */
+#define BX_MLP_MAX_LAYERS 8
+#define BX_MLP_MAX_WIDTH 256
+#define BX_MLP_MAX_IN 1024
+typedef struct bx_mlp {
+  int32_t n_layers;
+  int32_t activation;
+  int32_t in[BX_MLP_MAX_LAYERS];
+  int32_t out[BX_MLP_MAX_LAYERS];
+  const float* w[BX_MLP_MAX_LAYERS];
+  const float* b[BX_MLP_MAX_LAYERS];
+} bx_mlp;
+
+/* Where bx_mlp_backward writes layer l's gradients, shaped as w[l] and b[l];
+ * a null entry switches that gradient off. */
+typedef struct bx_mlp_grads {
+  float* dw[BX_MLP_MAX_LAYERS];
+  float* db[BX_MLP_MAX_LAYERS];
+} bx_mlp_grads;
+
+/* sizeof(bx_mlp) and sizeof(bx_mlp_grads) as the library was compiled */
+int bx_mlp_sizes(int32_t* mlp_bytes, int32_t* grads_bytes);
+
+/* The whole network in ONE launch, a workgroup per 32 rows, the tile's
+ * activations in LDS between layers. x is (rows, in[0]) with row pitch
+ * x_stride >= in[0] floats (a column slice of a wider buffer passes as it
+ * is); y is (rows, out[n_layers - 1]) contiguous. `saved` (NULL: not wanted)
+ * is (rows, H) contiguous, H the sum of the hidden layers' widths out[0 ..
+ * n_layers - 2]: every hidden layer's pre-activation, layer l's at column
+ * out[0] + .. + out[l - 1], which bx_mlp_backward reads. A null net, x or y
+ * (or weight or bias), n_layers, a width or an activation outside the limits
+ * above, in[l] != out[l - 1], x_stride < in[0] or rows < 0 fail before any
+ * device call; rows = 0 launches nothing. */
+int bx_mlp_forward(const bx_mlp* net, int64_t rows, const float* x, int64_t x_stride, float* y,
+                   float* saved, void* stream);
+
+/* The gradients of sum(y * dy) in at most TWO launches. dy is (rows,
+ * out[n_layers - 1]) contiguous, x and saved as bx_mlp_forward took and wrote
+ * them. Launch (i) runs the reverse chain per 32-row tile: dx (rows, in[0])
+ * contiguous when not NULL, and the hidden layers' pre-activation gradients
+ * dz into the workspace, (rows, H) as `saved`. Launch (ii) writes every layer's
+ * dW = a^T . dz and db = the column sums of dz that `grads` names (NULL: none),
+ * one workgroup per (layer, 32 x 64 tile of dW), a recomputed from saved (or x)
+ * as it is read. Launch (i) is left out when neither dx nor a hidden layer's
+ * gradient is wanted, launch (ii) when no gradient is. No floating-point
+ * atomics: each workgroup's 8 waves sum contiguous eighths of the rows in
+ * ascending order and the 8 partials are added in wave order, so the bits
+ * depend on (rows, shapes, inputs) alone.
+ *
+ * The workspace is the caller's (device memory, 16-byte aligned) of
+ * *workspace_bytes bytes; with workspace == NULL the call launches nothing
+ * and writes the size it needs to *workspace_bytes: max(16, 4 * rows * H).
+ * The failures of bx_mlp_forward, a null dy or workspace_bytes, a null saved
+ * with n_layers > 1, a workspace that is too small or misaligned fail before
+ * any device call; rows = 0 launches nothing. */
+int bx_mlp_backward(const bx_mlp* net, int64_t rows, const float* x, int64_t x_stride,
+                    const float* saved, const float* dy, float* dx, const bx_mlp_grads* grads,
+                    void* workspace, int64_t* workspace_bytes, void* stream);
+
 /*
  * Standalone HBM-streaming phase kernels over a structure-of-arrays batch
  * (the integrator and collider phases benchmarked in isolation).
