@@ -101,6 +101,7 @@ _SIGS = {
     'bx_mlp_sizes': abi.SIGNATURES['bx_mlp_sizes'],
     'bx_mlp_forward': abi.SIGNATURES['bx_mlp_forward'],
     'bx_mlp_backward': abi.SIGNATURES['bx_mlp_backward'],
+    'bx_ppo_head': abi.SIGNATURES['bx_ppo_head'],
 }
 
 EXPORTS = tuple(_SIGS)

@@ -206,6 +206,17 @@ MLP_BACKWARD_ARGS = (
     ('net', _mlp), ('rows', C.c_int64), ('x', _vp), ('x_stride', C.c_int64), ('saved', _vp),
     ('dy', _vp), ('dx', _vp), ('grads', C.POINTER(BxMlpGrads)), ('workspace', _vp),
     ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
+# bx_ppo_head: the (T, B, W) arrays are BxSeq with unit stride along a row
+PPO_HEAD_BLOCK = 256  # envs of a scan workgroup, rows of a row workgroup
+PPO_HEAD_ARGS = (
+    ('n_steps', C.c_int64), ('n_envs', C.c_int64), ('n_actions', C.c_int64), ('logits', _seq),
+    ('baseline', _seq), ('bootstrap', _vp), ('raw_action', _seq), ('eps', _seq),
+    ('log_prob', _seq), ('reward', _seq), ('done', _seq), ('truncation', _seq),
+    ('reward_scaling', C.c_float), ('discount', C.c_float), ('lambda', C.c_float),
+    ('clipping_epsilon', C.c_double), ('entropy_cost', C.c_float), ('min_std', C.c_float),
+    ('normalize_advantage', C.c_int), ('losses', _vp), ('dlogits', _seq), ('dbaseline', _seq),
+    ('vs', _seq), ('advantages', _seq), ('workspace', _vp),
+    ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
 PLAN_FIELDS = ('mode', 'lanes', 'lds_bytes', 'feat', 'gw', 'fold', 'jb', 'cb')  # bx_system_blob
 SYSTEM_BLOB_ARGS = (
     ('desc', _vp), ('reset', _vp), ('words', C.POINTER(C.c_uint32)), ('capacity', C.c_int64),
@@ -217,7 +228,7 @@ ARGS = {'bx_system_blob': SYSTEM_BLOB_ARGS,
         'bx_population_delta': POPULATION_DELTA_ARGS,
         'bx_replay_insert': REPLAY_INSERT_ARGS, 'bx_replay_sample': REPLAY_SAMPLE_ARGS,
         'bx_mlp_sizes': MLP_SIZES_ARGS, 'bx_mlp_forward': MLP_FORWARD_ARGS,
-        'bx_mlp_backward': MLP_BACKWARD_ARGS}
+        'bx_mlp_backward': MLP_BACKWARD_ARGS, 'bx_ppo_head': PPO_HEAD_ARGS}
 SIGNATURES = {name: ([t for _, t in args], C.c_int) for name, args in ARGS.items()}
 
 

@@ -11,6 +11,7 @@
 #include "../../include/brax_amd.h"
 #include "bx_blob.h"
 #include "mlp_launch.h"
+#include "ppo_head_launch.h"
 #include "pbd_features.h"
 #include "pbd_launch.h"
 #include "pbd_layout.h"
@@ -1285,6 +1286,82 @@ int bx_mlp_backward(const bx_mlp* net, int64_t rows, const float* x, int64_t x_s
   DeviceScope scope(dev);
   if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
   HIP_OK(launch_mlp_backward(m, g, rows, x, x_stride, saved, dy, dx, (float*)workspace, st));
+  return 0;
+}
+
+int bx_ppo_head(int64_t n_steps, int64_t n_envs, int64_t n_actions, const bx_seq* logits,
+                const bx_seq* baseline, const float* bootstrap, const bx_seq* raw_action,
+                const bx_seq* eps, const bx_seq* log_prob, const bx_seq* reward,
+                const bx_seq* done, const bx_seq* truncation, float reward_scaling, float discount,
+                float lambda, double clipping_epsilon, float entropy_cost, float min_std,
+                int normalize_advantage, float* losses, const bx_seq* dlogits,
+                const bx_seq* dbaseline, const bx_seq* vs, const bx_seq* advantages,
+                void* workspace, int64_t* workspace_bytes, void* stream) {
+  if (!workspace_bytes) return fail("null argument");
+  if (n_steps < 1) return fail("n_steps must be >= 1");
+  if (n_actions < 1) return fail("n_actions must be >= 1");
+  if (n_envs < 0) return fail("negative n_envs");
+  if (n_actions > ((int64_t)1 << 20)) return fail("too many actions");
+  if (n_steps > ((int64_t)1 << 31) || n_envs > ((int64_t)1 << 31) ||
+      n_steps * n_envs > ((int64_t)1 << 31))
+    return fail("too many rows for one launch");
+  const int64_t need = ppo_head_workspace_bytes(n_steps, n_envs);
+  if (!workspace) {  // the size query
+    *workspace_bytes = need;
+    return 0;
+  }
+  if (n_envs == 0) return 0;
+  const bx_seq* in[] = {logits, baseline, raw_action, eps, log_prob, reward, done, truncation};
+  for (const bx_seq* q : in)
+    if (!q || !q->ptr) return fail("null argument");
+  if (!bootstrap || !losses || !dlogits || !dlogits->ptr || !dbaseline || !dbaseline->ptr)
+    return fail("null argument");
+  const bx_seq none{nullptr, 0, 0};
+  if (!vs) vs = &none;
+  if (!advantages) advantages = &none;
+  // (a zero stride on an input broadcasts one row or column; on an output
+  // every step or env would write the same element)
+  for (const bx_seq* o : {dlogits, dbaseline, vs, advantages})
+    if (o->ptr && ((n_steps > 1 && o->time_stride == 0) || (n_envs > 1 && o->env_stride == 0)))
+      return fail("zero stride on an output");
+  if (*workspace_bytes < need)
+    return fail("workspace of " + std::to_string(*workspace_bytes) + " bytes, " +
+                std::to_string(need) + " needed");
+  if ((uintptr_t)workspace & 15) return fail("workspace not 16-byte aligned");
+  int dev = -1;
+  hipStream_t st = as_stream(stream);
+  if (st) HIP_OK(hipStreamGetDevice(st, &dev));
+  else HIP_OK(hipGetDevice(&dev));
+  DeviceScope scope(dev);
+  if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
+  PpoHeadArgs a{};
+  a.T = n_steps;
+  a.B = n_envs;
+  a.A = n_actions;
+  a.logits = *logits;
+  a.baseline = *baseline;
+  a.raw = *raw_action;
+  a.eps = *eps;
+  a.log_prob = *log_prob;
+  a.reward = *reward;
+  a.done = *done;
+  a.truncation = *truncation;
+  a.bootstrap = bootstrap;
+  a.reward_scaling = reward_scaling;
+  a.discount = discount;
+  a.lambda = lambda;
+  a.clip_lo = (float)(1.0 - clipping_epsilon);
+  a.clip_hi = (float)(1.0 + clipping_epsilon);
+  a.entropy_cost = entropy_cost;
+  a.min_std = min_std;
+  a.normalize = normalize_advantage != 0;
+  a.losses = losses;
+  a.dlogits = *dlogits;
+  a.dbaseline = *dbaseline;
+  a.vs = *vs;
+  a.adv = *advantages;
+  ppo_head_carve(a, workspace);
+  HIP_OK(launch_ppo_head(a, st));
   return 0;
 }
 

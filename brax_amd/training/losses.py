@@ -8,14 +8,14 @@ log-prob recomputed here for the recorded `raw_action` is the one the rollout
 kernel recorded, up to float32 rounding.
 """
 import dataclasses
-import math
 from typing import Any, Dict, Optional, Tuple
 
 import torch
 
-from brax_amd.envs.policy import head_scale, normal_tanh_log_prob, tanh_log_det
+from brax_amd.envs.policy import head_scale, normal_tanh_log_prob  # noqa: F401 (re-exported)
 from brax_amd.training.gae import compute_gae
 from brax_amd.training.networks import Layers, mlp
+from brax_amd.training.ppo_head import entropy, ppo_head  # noqa: F401 (entropy re-exported)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -53,20 +53,12 @@ def normalize(obs, normalizer):
   return (obs - mean.to(obs.dtype)) / std.to(obs.dtype)
 
 
-def entropy(loc, scale, eps):
-  """`ParametricDistribution.entropy` (`training/distribution.py:83-91`): the
-  Normal's entropy plus the tanh log-det at the sample loc + scale * eps,
-  summed over the actions."""
-  normal = 0.5 + (0.5 * math.log(2.0 * math.pi) + torch.log(scale))
-  return (normal + tanh_log_det(loc + scale * eps)).sum(-1)
-
-
 def ppo_loss(policy_layers: Layers, value_layers: Layers, normalizer, data: Transition, eps,
              entropy_cost: float = 1e-4, discounting: float = 0.9, reward_scaling: float = 1.0,
              gae_lambda: float = 0.95, clipping_epsilon: float = 0.3,
              normalize_advantage: bool = True, activation: str = 'swish', min_std: float = 1e-3,
              fused: Optional[bool] = None,
-             fused_mlp=False) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
+             fused_mlp=False, fused_head=False) -> Tuple[torch.Tensor, Dict[str, torch.Tensor]]:
   """`(loss, metrics)` of one minibatch.
 
   Args:
@@ -77,6 +69,10 @@ def ppo_loss(policy_layers: Layers, value_layers: Layers, normalizer, data: Tran
       reference's `rng`, explicit).
     fused: passed to `compute_gae`.
     fused_mlp: `networks.mlp`'s `fused` for the three network evaluations.
+    fused_head: `ppo_head.ppo_head`'s `fused` for everything after them (False:
+      chained torch; True: `bx_ppo_head` or NotImplementedError; None: the
+      kernel where it applies). The kernel runs its own GAE scan, so `fused`
+      is not consulted where it is taken.
   """
   data = data.map(lambda x: x.transpose(0, 1))  # time first
   eps = eps.transpose(0, 1)
@@ -85,24 +81,7 @@ def ppo_loss(policy_layers: Layers, value_layers: Layers, normalizer, data: Tran
   baseline = mlp(value_layers, obs, activation, fused_mlp).squeeze(-1)
   bootstrap_value = mlp(value_layers, normalize(data.next_observation[-1], normalizer),
                         activation, fused_mlp).squeeze(-1)
-  loc, s = torch.chunk(logits, 2, dim=-1)
-  scale = head_scale(s, min_std)
-  target_log_probs = normal_tanh_log_prob(loc, scale, data.raw_action).sum(-1)
-  # termination = (1 - discount) * (1 - truncation): compute_gae forms the
-  # product from done = 1 - discount; the reward scaling is folded in as well
-  vs, advantages = compute_gae(
-      truncation=data.truncation, termination=1 - data.discount, rewards=data.reward,
-      values=baseline, bootstrap_value=bootstrap_value, lambda_=gae_lambda,
-      discount=discounting, reward_scaling=reward_scaling, fused=fused)
-  if normalize_advantage:
-    advantages = (advantages - advantages.mean()) / (advantages.std(unbiased=False) + 1e-8)
-  rho_s = torch.exp(target_log_probs - data.log_prob)
-  surrogate_loss1 = rho_s * advantages
-  surrogate_loss2 = torch.clamp(rho_s, 1 - clipping_epsilon, 1 + clipping_epsilon) * advantages
-  policy_loss = -torch.mean(torch.minimum(surrogate_loss1, surrogate_loss2))
-  v_error = vs - baseline
-  v_loss = torch.mean(v_error * v_error) * 0.5 * 0.5
-  entropy_loss = entropy_cost * -torch.mean(entropy(loc, scale, eps.to(loc.dtype)))
-  total_loss = policy_loss + v_loss + entropy_loss
-  return total_loss, {'total_loss': total_loss, 'policy_loss': policy_loss, 'v_loss': v_loss,
-                      'entropy_loss': entropy_loss}
+  return ppo_head(logits, baseline, bootstrap_value, data, eps, entropy_cost=entropy_cost,
+                  discounting=discounting, reward_scaling=reward_scaling, gae_lambda=gae_lambda,
+                  clipping_epsilon=clipping_epsilon, normalize_advantage=normalize_advantage,
+                  min_std=min_std, fused=fused_head, fused_gae=fused, gae=compute_gae)

@@ -28,6 +28,7 @@ from brax_amd.envs.policy import MLPPolicy, policy_rollout
 from brax_amd.envs.population import update_running_statistics
 from brax_amd.training import networks as ppo_networks
 from brax_amd.training.losses import Transition, ppo_loss
+from brax_amd.training.ppo_head import METRICS
 
 
 @dataclasses.dataclass(frozen=True)
@@ -115,7 +116,8 @@ class Learner:
                clipping_epsilon: float = 0.3, gae_lambda: float = 0.95,
                normalize_observations: bool = False, normalize_advantage: bool = True,
                seed: int = 0, network_factory=ppo_networks.make_ppo_networks, device=None,
-               fused_gae: Optional[bool] = None, action_repeat: int = 1, fused_mlp=False):
+               fused_gae: Optional[bool] = None, action_repeat: int = 1, fused_mlp=False,
+               fused_head=False):
     assert batch_size * num_minibatches % num_envs == 0
     self.env, self.device = env, torch.device(device)
     self.action_repeat = int(action_repeat)
@@ -124,6 +126,7 @@ class Learner:
     self.num_updates_per_batch = int(num_updates_per_batch)
     self.unrolls = batch_size * num_minibatches // num_envs
     self.seed, self.fused_gae, self.fused_mlp = int(seed), fused_gae, fused_mlp
+    self.fused_head = fused_head
     self.loss_kwargs = dict(entropy_cost=entropy_cost, discounting=discounting,
                             reward_scaling=reward_scaling, gae_lambda=gae_lambda,
                             clipping_epsilon=clipping_epsilon,
@@ -193,7 +196,7 @@ class Learner:
     steps; returns the mean of each loss metric (device tensors)."""
     n, bs = data.reward.shape[0], self.batch_size
     A = data.action.shape[-1]
-    sums = {}
+    sums, vector = {}, None
     for _ in range(self.num_updates_per_batch):
       perm = torch.randperm(n, generator=self._gen, device=self.device)
       shuffled = data.map(lambda x, perm=perm: x[perm])
@@ -202,14 +205,21 @@ class Learner:
         eps = torch.randn((bs, self.unroll_length, A), generator=self._gen, device=self.device)
         loss, metrics = ppo_loss(self.policy_layers, self.value_layers, self._mean_std, mb, eps,
                                  fused=self.fused_gae, fused_mlp=self.fused_mlp,
-                                 **self.loss_kwargs)
+                                 fused_head=self.fused_head, **self.loss_kwargs)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.optimizer.step()
-        for k, v in metrics.items():
-          sums[k] = v.detach() + sums.get(k, 0)
+        if getattr(metrics, 'vector', None) is not None:
+          # the fused head's four metrics are one (4,) tensor: one add, not four
+          vector = metrics.vector if vector is None else vector + metrics.vector
+        else:
+          for k, v in metrics.items():
+            sums[k] = v.detach() + sums.get(k, 0)
     self.actor.load_(_detached(self.policy_layers))
     steps = self.num_updates_per_batch * self.num_minibatches
+    if vector is not None:
+      for k, name in enumerate(METRICS):
+        sums[name] = vector[k] + sums.get(name, 0)
     return {k: v / steps for k, v in sums.items()}
 
   def training_step(self):
@@ -230,7 +240,7 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
           deterministic_eval: bool = False, network_factory=ppo_networks.make_ppo_networks,
           progress_fn: Callable[[int, dict], None] = lambda *args: None,
           normalize_advantage: bool = True, eval_env=None, device=None,
-          fused_gae: Optional[bool] = None, fused_mlp=False):
+          fused_gae: Optional[bool] = None, fused_mlp=False, fused_head=False):
   """PPO training; the reference's arguments and defaults
   (`ppo/train.py:61-86`).
 
@@ -245,6 +255,10 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
     fused_mlp: the loss's networks through `fused_mlp.fused_mlp` (False: chained
       torch; True: the kernels or NotImplementedError; None: the kernels where
       they apply).
+    fused_head: the loss after the networks through `ppo_head.ppo_head` (False:
+      chained torch; True: `bx_ppo_head` or NotImplementedError; None: the
+      kernel where it applies); where the kernel is taken it runs its own GAE
+      scan and `fused_gae` is not consulted.
   Returns:
     `(make_policy, params, metrics)`: `make_policy(params, deterministic=False)`
     gives an `MLPPolicy`; `params` is (the normaliser or None, the policy
@@ -273,7 +287,7 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
                     normalize_observations=normalize_observations,
                     normalize_advantage=normalize_advantage, seed=seed,
                     network_factory=network_factory, device=dev, fused_gae=fused_gae,
-                    action_repeat=action_repeat, fused_mlp=fused_mlp)
+                    action_repeat=action_repeat, fused_mlp=fused_mlp, fused_head=fused_head)
   key = np.array([0, int(seed)], np.uint32)  # jax.random.PRNGKey(seed) layout
   key_env, key_eval = wrappers.split_key(key)
   learner.reset(key_env)

@@ -871,6 +871,72 @@ int bx_mlp_backward(const bx_mlp* net, int64_t rows, const float* x, int64_t x_s
                     const float* saved, const float* dy, float* dx, const bx_mlp_grads* grads,
                     void* workspace, int64_t* workspace_bytes, void* stream);
 
+/* The PPO loss head: everything of `compute_ppo_loss` (training/agents/ppo/
+ * losses.py:96-182) between the two networks' outputs and the scalar loss,
+ * and the loss's gradients in `logits` and `baseline`, in TWO launches.
+ * float32. The (T, B) arrays are bx_seq views as bx_compute_gae takes them; a
+ * (T, B, W) array is a bx_seq whose element (t, e) is the row of W floats at
+ * ptr + t * time_stride + e * env_stride, the row itself with UNIT stride
+ * (logits and dlogits: W = 2 A, the A locations then the A scale parameters;
+ * raw_action and eps: W = A). bootstrap is (B,) contiguous. With N = T * B:
+ *   scale      = softplus(s) + min_std      (softplus(x) = x above 20, else
+ *                                            log1p(exp(x)))
+ *   det(x)     = 2 (log 2 - x - softplus(-2 x))
+ *   lp[t, e]   = sum_a -0.5 z^2 - 0.5 log 2 pi - log scale - det(raw),
+ *                z = (raw - loc) / scale
+ *   vs, adv    = bx_compute_gae(reward, done, truncation, values = baseline,
+ *                bootstrap, reward_scaling, discount, lambda), bit for bit
+ *   A^         = normalize_advantage ? (adv - mean) / (std + 1e-8) : adv, the
+ *                mean and the population standard deviation over all N
+ *   rho        = exp(lp - log_prob)
+ *   losses[1]  = -1/N sum min(rho A^, clamp(rho, 1 - clipping_epsilon,
+ *                1 + clipping_epsilon) A^)                    (policy)
+ *   losses[2]  = 0.25/N sum (vs - baseline)^2                 (v)
+ *   losses[3]  = -entropy_cost/N sum sum_a [0.5 + 0.5 log 2 pi + log scale +
+ *                det(loc + scale eps)]                        (entropy)
+ *   losses[0]  = losses[1] + losses[2] + losses[3]            (total)
+ * dlogits (T, B, 2 A) and dbaseline (T, B) are d losses[0] / d logits and
+ * / d baseline with vs and adv held constant (the reference stops their
+ * gradient, so bootstrap has none): dbaseline = -0.5 (vs - baseline) / N; in
+ * rho the surrogate's derivative is A^ times what autograd's minimum and clamp
+ * give (1 on the closed clip interval and where the unclipped product is the
+ * strictly smaller one, a half where the two products tie outside it, else 0).
+ * vs and advantages (NULL, or a null ptr: not wanted) receive the GAE outputs
+ * before normalisation. clipping_epsilon is a double so that the interval's
+ * ends are (float)(1 -+ clipping_epsilon) as a float32 tensor's clamp has them.
+ *
+ * Launch 1: a workgroup per 256 envs runs the scan, one lane per env, and
+ * writes dbaseline; a workgroup per 256 (t, e) rows sums lp and the entropy
+ * over the actions, one lane per row. Launch 2: a workgroup per 256 rows writes
+ * dlogits and one more sums the losses. No floating-point atomics: every sum
+ * across rows is float64, lane-strided in ascending order and then added over
+ * lanes and waves in a fixed tree, workgroup partials in workgroup order, so
+ * the bits depend on (T, B, A) and the inputs alone. The standard deviation
+ * comes from per-workgroup (count, mean, centred square sum) triples combined
+ * pairwise, not from a sum of squares. NaN and Inf propagate as IEEE has
+ * them; a non-finite input of env e reaches no other env's dbaseline, vs or
+ * advantages (through the mean it reaches every dlogits when normalising).
+ *
+ * The workspace is the caller's (device memory, 16-byte aligned) of
+ * *workspace_bytes bytes; with workspace == NULL the call launches nothing
+ * and writes the size it needs to *workspace_bytes: 8 (4 ceil(B / 256) +
+ * ceil(N / 256)) + 8 N, rounded up to 16. The outputs may have any layout (but
+ * unit stride along a row) and must not overlap the inputs, the workspace or
+ * each other. A null workspace_bytes, n_steps < 1, n_actions < 1, n_envs < 0,
+ * more than 2^31 rows or 2^20 actions, a null pointer, a zero stride on an
+ * output, a workspace that is too small or misaligned fail before any device
+ * call; n_envs = 0 launches nothing. No system handle: the launches go to the
+ * device that owns `stream` (the current device for NULL). (Additive: no ABI
+ * bump.) */
+int bx_ppo_head(int64_t n_steps, int64_t n_envs, int64_t n_actions, const bx_seq* logits,
+                const bx_seq* baseline, const float* bootstrap, const bx_seq* raw_action,
+                const bx_seq* eps, const bx_seq* log_prob, const bx_seq* reward,
+                const bx_seq* done, const bx_seq* truncation, float reward_scaling,
+                float discount, float lambda, double clipping_epsilon, float entropy_cost,
+                float min_std, int normalize_advantage, float* losses, const bx_seq* dlogits,
+                const bx_seq* dbaseline, const bx_seq* vs, const bx_seq* advantages,
+                void* workspace, int64_t* workspace_bytes, void* stream);
+
 /*
  * Standalone HBM-streaming phase kernels over a structure-of-arrays batch
  * (the integrator and collider phases benchmarked in isolation).
