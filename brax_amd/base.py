@@ -195,6 +195,20 @@ def packed_buffer(qp):
   return None
 
 
+def pack_qp(qp, dev):
+  """The contiguous float32 (…, N, 16) buffer of any QP on `dev`: the one
+  behind a packed QP (no copy when it already is all of that), else the
+  fields written into a fresh zero buffer."""
+  buf = packed_buffer(qp)
+  if buf is None:
+    buf = torch.zeros(qp.pos.shape[:-1] + (16,), dtype=torch.float32, device=dev)
+    for lo, f in ((0, qp.pos), (3, qp.rot), (7, qp.vel), (10, qp.ang)):
+      buf[..., lo:lo + f.shape[-1]] = f
+  if buf.dtype != torch.float32 or buf.device != dev or not buf.is_contiguous():
+    buf = buf.to(dev, torch.float32).contiguous()
+  return buf
+
+
 def qp_from_numpy(a, device):
   """(…, N, 13) array -> packed QP on `device`."""
   t = torch.as_tensor(a, dtype=torch.float32)

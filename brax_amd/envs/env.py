@@ -181,6 +181,7 @@ class PhysicsEnv(Env):
     if m.value != len(self.metric_keys):
       raise RuntimeError(f'{type(self).__name__}: {m.value} metrics, {len(self.metric_keys)} keys')
     self.obs_size = o.value
+    self.__dict__.pop('_layouts', None)  # (packed.layout's, built on the sizes)
 
   def _params(self, opts=None, first_qp=None, first_obs=None):
     opts = opts or {}
@@ -345,20 +346,12 @@ class PhysicsEnv(Env):
       raise ValueError(f'action shape {tuple(act.shape)} != {(B, self.action_size)}')
     if act.stride(-1) != 1:
       act = act.contiguous()
-    auto = bool(opts.get('auto_reset'))
-    first_qp = state.info.get('first_qp') if auto else None
-    first_obs = state.info.get('first_obs') if auto else None
-    if auto and (first_qp is None or first_obs is None):
-      raise ValueError('AutoResetWrapper state lacks first_qp / first_obs')
-    p = self._cached_params(opts, first_qp, first_obs)
+    p, done_in, steps_in, rng_in = packed.step_inputs(self, opts, state, B)
     qp, obs, scal, met = self._alloc(B)
     sin = abi.BxEnvState()
     sin.qp = qp_struct(state.qp, True)
-    done_in = _f32(state.done, dev)
     sin.done = done_in.data_ptr()
-    steps_in = state.info.get('steps')
     if steps_in is not None:
-      steps_in = _f32(steps_in, dev)
       sin.steps = steps_in.data_ptr()
     sout = abi.BxEnvState()
     sout.qp = qp_struct(qp, True)
@@ -369,9 +362,6 @@ class PhysicsEnv(Env):
     sout.steps = base + 8 * B
     sout.truncation = base + 12 * B
     sout.metrics = met.data_ptr()
-    rng_in = state.info.get('rng')
-    if rng_in is None and getattr(self, 'needs_rng', False):
-      rng_in = torch.zeros((B,), dtype=torch.int32, device=dev)  # a state built by hand
     rng_out = None
     if rng_in is not None:  # the target envs' per-env streams (int32 (B,))
       sin.rng = rng_in.data_ptr()
@@ -411,43 +401,17 @@ def _step_packed_impl(self, state, action, opts):
     act = act.contiguous()
   if qbuf.dtype != torch.float32 or not qbuf.is_cuda or not qbuf.is_contiguous():
     qbuf = qbuf.contiguous().float()
-  info_in = state.info
-  auto = bool(opts.get('auto_reset'))
-  first_qp = info_in.get('first_qp') if auto else None
-  first_obs = info_in.get('first_obs') if auto else None
-  if auto and (first_qp is None or first_obs is None):
-    raise ValueError('AutoResetWrapper state lacks first_qp / first_obs')
-  p = self._cached_params(opts, first_qp, first_obs)
-  done_in = _f32(state.done, dev)
-  steps_in = info_in.get('steps')
-  if steps_in is not None:
-    steps_in = _f32(steps_in, dev)
-  rng_in = info_in.get('rng')
-  if rng_in is None and getattr(self, 'needs_rng', False):
-    rng_in = torch.zeros((B,), dtype=torch.int32, device=dev)  # a state built by hand
+  p, done_in, steps_in, rng_in = packed.step_inputs(self, opts, state, B)
   rng_out = torch.empty_like(rng_in) if rng_in is not None else None
-  N, O, M = self.sys.num_bodies, self.obs_size, len(self.metric_keys)
-  out = torch.empty((B * (N * 16 + O + 4 + M),), dtype=torch.float32, device=dev)
+  lay = packed.layout(self, B)
+  out = torch.empty((lay.block,), dtype=torch.float32, device=dev)
   _native.check(_native.lib().bx_env_step_packed(
       self.sys._h, C.byref(p), B, qbuf.data_ptr(), done_in.data_ptr(),  # pylint: disable=protected-access
       None if steps_in is None else steps_in.data_ptr(),
       None if rng_in is None else rng_in.data_ptr(), act.data_ptr(), act.stride(0),
       act.shape[1], out.data_ptr(), None if rng_out is None else rng_out.data_ptr(),
       _stream(dev.index)))
-  q, obs, reward, done, steps, trunc, met = torch.split(out, (B * N * 16, B * O, B, B, B, B, B * M))
-  info = dict(info_in)
-  if p.episode_length > 0:
-    info['steps'] = steps
-    info['truncation'] = trunc
-  if rng_out is not None:
-    info['rng'] = rng_out
-  keys = self.metric_keys
-  m_in = state.metrics
-  extra = m_in.carried(keys) if type(m_in) is _Metrics else {
-      k: v for k, v in m_in.items() if k not in keys}
-  metrics = _Metrics(met.view(B, M) if M else None, keys, extra)
-  return State(qp=PackedQP(q.view(B, N, 16)), obs=obs.view(B, O), reward=reward, done=done,
-               metrics=metrics, info=info)
+  return packed.final_state(self, p, state, lay.step_views(out), rng_out)
 
 
 def _f32(x, dev):
@@ -455,3 +419,7 @@ def _f32(x, dev):
   if type(x) is torch.Tensor and x.dtype == torch.float32 and x.is_cuda and x.is_contiguous():
     return x
   return torch.as_tensor(x, dtype=torch.float32, device=dev).contiguous()
+
+
+# at the end: packed.py builds the States of this module
+from brax_amd.envs import packed  # noqa: E402  pylint: disable=wrong-import-position

@@ -21,11 +21,12 @@ import numpy as np
 import torch
 
 from brax_amd import _native, abi
-from brax_amd.base import PackedQP
-from brax_amd.envs import wrappers
-from brax_amd.envs.env import State, _f32, _Metrics
-from brax_amd.envs.policy import MLPPolicy, _packed, _stream, fused_supported, normal_slabs
+from brax_amd.base import pack_qp
+from brax_amd.envs import packed, wrappers
+from brax_amd.envs.env import State
+from brax_amd.envs.policy import MLPPolicy, fused_supported, step_noise
 from brax_amd.envs.rollout import chain_options
+from brax_amd.system import _stream
 
 
 def eval_keys(metric_keys):
@@ -77,23 +78,16 @@ def eval_supported(env, policy=None) -> Optional[str]:
     u, opts = chain_options(inner)
   except NotImplementedError as e:
     return str(e)
-  p = u._params(opts, None, None)  # pylint: disable=protected-access
-  p.auto_reset = 0
-  lib = _native.lib()
-  if policy is not None and policy.head != 'normal_tanh':
-    desc = policy.descriptor(u.action_size)
+  if policy is None:
+    return packed.refusal(u, opts, 'bx_env_eval_packed', 0, 0, None, None, None, None, None, 0, 0,
+                          u.action_size, None, None, None, None, None)
+  desc = policy.descriptor(u.action_size)
+  if policy.head != 'normal_tanh':
     pop = abi.BxPopulation(head=abi.HEADS[policy.head])
-    rc = lib.bx_env_eval_population(u.sys._h, C.byref(p), 0, 0, None, None, None, None, None,  # pylint: disable=protected-access
-                                    C.byref(desc), 0, 0, 0, None, None, None, None,
-                                    C.byref(pop), None)
-  elif policy is not None:
-    desc = policy.descriptor(u.action_size)
-    rc = lib.bx_env_eval_policy(u.sys._h, C.byref(p), 0, 0, None, None, None, None, None,  # pylint: disable=protected-access
-                                C.byref(desc), 0, 0, 0, None, None, None, None, None)
-  else:
-    rc = lib.bx_env_eval_packed(u.sys._h, C.byref(p), 0, 0, None, None, None, None, None, 0, 0,  # pylint: disable=protected-access
-                                u.action_size, None, None, None, None, None)
-  return None if rc == 0 else lib.bx_last_error().decode()
+    return packed.refusal(u, opts, 'bx_env_eval_population', 0, 0, None, None, None, None, None,
+                          C.byref(desc), 0, 0, 0, None, None, None, None, C.byref(pop), None)
+  return packed.refusal(u, opts, 'bx_env_eval_policy', 0, 0, None, None, None, None, None,
+                        C.byref(desc), 0, 0, 0, None, None, None, None, None)
 
 
 def eval_rollout(env, state: State, k: Optional[int] = None, policy: Optional[MLPPolicy] = None,
@@ -114,8 +108,9 @@ def eval_rollout(env, state: State, k: Optional[int] = None, policy: Optional[ML
       `env.step`, per step); True raises NotImplementedError where the kernel
       refuses; False forces the chained path.
     out, eval_out: optional buffers for the fused launch to write: a flat
-      contiguous float32 of B * (N*16 + O + 4 + M) floats and a contiguous
-      float32 (M + 3, B); the returned state's tensors are views of them.
+      contiguous float32 of one block (`packed.Layout.block` floats) and a
+      contiguous float32 (M + 3, B); the returned state's tensors are views of
+      them.
   Returns:
     The state `EvalWrapper.step` returns after the K-th step: `metrics`
     includes 'reward', `info['eval_metrics']` is an `EvalMetrics` over views
@@ -143,33 +138,16 @@ def eval_rollout(env, state: State, k: Optional[int] = None, policy: Optional[ML
     return _chained(env, state, policy, actions, K, seed, offset, step_stride)
   u, opts = chain_options(inner)
   dev = u.sys.device
-  qbuf = _packed(state, dev)
+  qbuf = pack_qp(state.qp, dev)
   B, A = qbuf.shape[0], u.action_size
-  auto = bool(opts.get('auto_reset'))
-  info_in = state.info
-  first_qp = info_in.get('first_qp') if auto else None
-  first_obs = info_in.get('first_obs') if auto else None
-  if auto and (first_qp is None or first_obs is None):
-    raise ValueError('AutoResetWrapper state lacks first_qp / first_obs')
-  p = u._cached_params(opts, first_qp, first_obs)  # pylint: disable=protected-access
-  done_in = _f32(state.done, dev)
-  steps_in = info_in.get('steps')
-  if steps_in is not None:
-    steps_in = _f32(steps_in, dev)
-  rng_in = info_in.get('rng')
-  if rng_in is None and getattr(u, 'needs_rng', False):
-    rng_in = torch.zeros((B,), dtype=torch.int32, device=dev)
+  p, done_in, steps_in, rng_in = packed.step_inputs(u, opts, state, B)
   keys = tuple(u.metric_keys)
-  N, O, M = u.sys.num_bodies, u.obs_size, len(keys)
+  M = len(keys)
   ev = pack_eval_metrics(em_in, keys, dev)
   if tuple(ev.shape) != (M + 3, B):
     raise ValueError(f'eval_metrics holds {ev.shape[1]} envs, the state {B}')
-  block = B * (N * 16 + O + 4 + M)
-  if out is None:
-    out = torch.empty((block,), dtype=torch.float32, device=dev)
-  elif (out.numel() < block or out.dtype != torch.float32 or not out.is_contiguous()
-        or out.device != dev):
-    raise ValueError(f'out must hold {block} contiguous float32 on {dev}')
+  lay = packed.layout(u, B)
+  out = lay.out_buffer(out, 1, dev)
   if eval_out is not None:
     if (tuple(eval_out.shape) != (M + 3, B) or eval_out.dtype != torch.float32
         or not eval_out.is_contiguous() or eval_out.device != dev):
@@ -180,11 +158,7 @@ def eval_rollout(env, state: State, k: Optional[int] = None, policy: Optional[ML
   lib = _native.lib()
   if policy is not None:
     stride = 2 * B * A if step_stride is None else int(step_stride)
-    obs_in = _f32(state.obs, dev)
-    if not obs_in.is_contiguous():
-      obs_in = obs_in.contiguous()
-    if tuple(obs_in.shape) != (B, O):
-      raise ValueError(f'state.obs {tuple(obs_in.shape)} != ({B}, {O})')
+    obs_in = packed.obs_input(u, state, B)
     desc = policy.descriptor(A)
     if policy.head != 'normal_tanh':
       # ARS's policy: the population kernel with one shared row, no moments
@@ -210,21 +184,8 @@ def eval_rollout(env, state: State, k: Optional[int] = None, policy: Optional[ML
         u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), done_in.data_ptr(), ptr(steps_in),  # pylint: disable=protected-access
         ptr(rng_in), act.data_ptr(), act.stride(1), act.stride(0), A, ev.data_ptr(),
         out.data_ptr(), ev.data_ptr(), ptr(rng_out), _stream(dev.index)))
-  q, obs, sc, met = torch.split(out[:block], (B * N * 16, B * O, 4 * B, B * M))
-  sc = sc.view(4, B)
-  info = dict(info_in)
-  if p.episode_length > 0:
-    info['steps'] = sc[2]
-    info['truncation'] = sc[3]
-  if rng_out is not None:
-    info['rng'] = rng_out
-  info['eval_metrics'] = unpack_eval_metrics(ev, keys)
-  m_in = state.metrics
-  extra = dict(m_in.carried(keys) if type(m_in) is _Metrics else {
-      kk: v for kk, v in m_in.items() if kk not in keys})
-  extra['reward'] = sc[0]
-  return State(qp=PackedQP(q.view(B, N, 16)), obs=obs.view(B, O), reward=sc[0], done=sc[1],
-               metrics=_Metrics(met.view(B, M) if M else None, keys, extra), info=info)
+  return packed.final_state(u, p, state, lay.step_views(out[:lay.block]), rng_out,
+                            eval_metrics=unpack_eval_metrics(ev, keys))
 
 
 def _chained(env, state, policy, actions, K, seed, offset, step_stride):
@@ -237,13 +198,8 @@ def _chained(env, state, policy, actions, K, seed, offset, step_stride):
     return state
   policy.for_actions(A)
   stride = 2 * B * A if step_stride is None else int(step_stride)
-  eps = torch.zeros((K, B, A), dtype=torch.float32, device=dev)
-  if not policy.deterministic and policy.head == 'normal_tanh':  # (an identity head draws none)
-    for t in range(K):
-      normal_slabs(eps[t], B * A, 1, seed, offset + t * stride, 0)
-  for t in range(K):
-    a = policy.forward(state.obs.to(torch.float32), eps[t])[0]
-    state = env.step(state, a)
+  for eps in step_noise(policy, K, B, A, seed, offset, stride, dev):
+    state = env.step(state, policy.forward(state.obs.to(torch.float32), eps)[0])
   return state
 
 

@@ -1,7 +1,7 @@
 """hipGraph-captured Env.step rollouts.
 
 The reference compiles `env.step` with `jax.jit` and calls the executable in
-a Python loop (`/root/reference/notebooks/environments.ipynb:386-423`); each
+a Python loop (`notebooks/environments.ipynb:386-423`); each
 call is one device dispatch. Here one `Env.step` is already one fused kernel
 launch through the C ABI, but the ~20 µs of Python per step (the wrapper
 chain, the State, the ctypes call, the action draw's launch) can exceed the
@@ -27,7 +27,7 @@ import ctypes as C
 import torch
 
 from brax_amd import _native
-from brax_amd.base import PackedQP, packed_buffer
+from brax_amd.base import PackedQP, pack_qp, packed_buffer
 from brax_amd.envs.env import State
 from brax_amd.system import _stream
 
@@ -36,7 +36,76 @@ def _static(x):
   return None if x is None else x.detach().clone().contiguous()
 
 
-class StepGraph:
+class _Captured:
+  """What `StepGraph` and `RolloutGraph` share: the static inputs their
+  captured `body` reads and feeds back, and the capture recipe."""
+
+  def _static_inputs(self, u, state):
+    """Copies exactly the tensors `Env.step` reads (the QP, done, the episode
+    counters, the target envs' streams) into static inputs and makes `_in`,
+    the state over them; first_qp / first_obs pass through by reference.
+    Returns the batch size."""
+    dev = self.device
+    self._qp = _static(pack_qp(state.qp, dev))
+    B = self._qp.shape[0]
+    self._done = _static(state.done)
+    info = dict(state.info)
+    self._steps = _static(info.get('steps'))
+    rng = info.get('rng')
+    if rng is None and getattr(u, 'needs_rng', False):
+      # a hand-built state of a target env: the step would start a zero
+      # stream per call; make it a static input so replays advance it
+      rng = torch.zeros((B,), dtype=torch.int32, device=dev)
+    self._rng = _static(rng)
+    if self._steps is not None:
+      info['steps'] = self._steps
+    if self._rng is not None:
+      info['rng'] = self._rng
+    self._in = State(qp=PackedQP(self._qp), obs=state.obs, reward=state.reward,
+                     done=self._done, metrics=state.metrics, info=info)
+    self._epoch = torch.zeros((1,), dtype=torch.int64, device=dev)
+    return B
+
+  def _feed_back(self, st):
+    """Recorded at the end of `body`: the state it reached becomes the static
+    inputs of the next replay, and the epoch advances."""
+    self._qp.copy_(packed_buffer(st.qp))
+    self._done.copy_(st.done)
+    if self._steps is not None:
+      self._steps.copy_(st.info['steps'])
+    if self._rng is not None:
+      self._rng.copy_(st.info['rng'])
+    self._epoch.add_(1)
+
+  def _capture(self, body):
+    """Captures `body()` into `self.graph`; returns what it returned."""
+    dev = self.device
+    with torch.cuda.device(dev):
+      # one eager pass on a side stream fills the host-side caches (the env's
+      # parameter block) and the allocator, as torch's capture recipe asks;
+      # the state it produces is discarded and the statics restored. The hook
+      # is left out of it (its side effects would count K extra steps).
+      statics = [t for t in (self._qp, self._done, self._steps, self._rng) if t is not None]
+      snap = [t.clone() for t in statics]
+      side = torch.cuda.Stream(dev)
+      side.wait_stream(torch.cuda.current_stream(dev))
+      with torch.cuda.stream(side):
+        body(hook=None)
+      torch.cuda.current_stream(dev).wait_stream(side)
+      for dst, src in zip(statics, snap):
+        dst.copy_(src)
+      self._epoch.zero_()
+      self.graph = torch.cuda.CUDAGraph()
+      # thread_local: only this thread's calls are checked during capture, so
+      # a process group's watchdog thread polling its collectives' events (the
+      # bench's barrier just before) cannot invalidate the capture
+      with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
+        res = body()
+      torch.cuda.current_stream(dev).synchronize()
+    return res
+
+
+class StepGraph(_Captured):
   """K `env.step` calls with on-device action draws, captured as one graph.
 
   Args:
@@ -67,37 +136,11 @@ class StepGraph:
     u = env.unwrapped
     dev = u.sys.device
     self.env, self.k, self.device, self.draw = env, int(k), dev, draw
-    buf = packed_buffer(state.qp)
-    B = (buf if buf is not None else state.qp.pos).shape[0]
+    B = self.batch_size = self._static_inputs(u, state)
     A = env.action_size
-    self.batch_size = B
     stride = B * A if step_stride is None else int(step_stride)
-    # static inputs: exactly the tensors Env.step reads (the QP, done, the
-    # episode counters, the target envs' streams); first_qp / first_obs pass
-    # through by reference
-    if buf is None:
-      buf = torch.zeros(state.qp.pos.shape[:-1] + (16,), dtype=torch.float32, device=dev)
-      for lo_, f in ((0, state.qp.pos), (3, state.qp.rot), (7, state.qp.vel), (10, state.qp.ang)):
-        buf[..., lo_:lo_ + f.shape[-1]] = f
-    self._qp = _static(buf)
-    self._done = _static(state.done)
-    info = dict(state.info)
-    self._steps = _static(info.get('steps'))
-    rng = info.get('rng')
-    if rng is None and getattr(u, 'needs_rng', False):
-      # a hand-built state of a target env: the step would start a zero
-      # stream per call; make it a static input so replays advance it
-      rng = torch.zeros((B,), dtype=torch.int32, device=dev)
-    self._rng = _static(rng)
-    if self._steps is not None:
-      info['steps'] = self._steps
-    if self._rng is not None:
-      info['rng'] = self._rng
-    self._in = State(qp=PackedQP(self._qp), obs=state.obs, reward=state.reward,
-                     done=self._done, metrics=state.metrics, info=info)
     self._acts = torch.empty((self.k if draw == 'batched' else 1, B, A), dtype=torch.float32,
                              device=dev)
-    self._epoch = torch.zeros((1,), dtype=torch.int64, device=dev)
     lib = _native.lib()
 
     def draw_slabs(first, n):
@@ -115,38 +158,10 @@ class StepGraph:
         st = env.step(st, self._acts[t if self.draw == 'batched' else 0])
         if hook is not None:
           hook(st)
-      # feed the K-th state back into the static inputs, advance the epoch
-      self._qp.copy_(packed_buffer(st.qp))
-      self._done.copy_(st.done)
-      if self._steps is not None:
-        self._steps.copy_(st.info['steps'])
-      if self._rng is not None:
-        self._rng.copy_(st.info['rng'])
-      self._epoch.add_(1)
+      self._feed_back(st)
       return st
 
-    with torch.cuda.device(dev):
-      # one eager pass on a side stream fills the host-side caches (the env's
-      # parameter block) and the allocator, as torch's capture recipe asks;
-      # the state it produces is discarded and the statics restored. The hook
-      # is left out of it (its side effects would count K extra steps).
-      statics = [t for t in (self._qp, self._done, self._steps, self._rng) if t is not None]
-      snap = [t.clone() for t in statics]
-      side = torch.cuda.Stream(dev)
-      side.wait_stream(torch.cuda.current_stream(dev))
-      with torch.cuda.stream(side):
-        body(hook=None)
-      torch.cuda.current_stream(dev).wait_stream(side)
-      for dst, src in zip(statics, snap):
-        dst.copy_(src)
-      self._epoch.zero_()
-      self.graph = torch.cuda.CUDAGraph()
-      # thread_local: only this thread's calls are checked during capture, so
-      # a process group's watchdog thread polling its collectives' events (the
-      # bench's barrier just before) cannot invalidate the capture
-      with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
-        self._out = body()
-      torch.cuda.current_stream(dev).synchronize()
+    self._out = self._capture(body)
 
   @property
   def epoch(self) -> int:

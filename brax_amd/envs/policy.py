@@ -23,9 +23,11 @@ from typing import Any, Optional, Tuple
 import torch
 
 from brax_amd import _native, abi
-from brax_amd.base import PackedQP, packed_buffer
-from brax_amd.envs.env import State, _f32, _Metrics
-from brax_amd.envs.rollout import Trajectory, chain_options
+from brax_amd.base import pack_qp
+from brax_amd.envs import packed
+from brax_amd.envs.env import State, _f32
+from brax_amd.envs.rollout import Trajectory, chain_options, trajectory
+from brax_amd.system import _stream
 
 _ACTIVATIONS = {
     'swish': torch.nn.functional.silu,
@@ -62,9 +64,20 @@ class PolicyExtras:
   log_prob: Any
 
 
-def _stream(index):
-  from brax_amd.system import _stream as s  # pylint: disable=import-outside-toplevel
-  return s(index)
+def normal_tanh_head(policy, logits, eps=None):
+  """`policy`'s NormalTanh head over its last layer's output: (action, raw,
+  loc, scale) with raw = loc + scale * eps and action = tanh(raw); `eps` is
+  zeros when None or when the policy is deterministic, scale ones when the
+  head has no scale half."""
+  if policy._loc_only():  # pylint: disable=protected-access
+    loc, scale = logits, torch.ones_like(logits)
+  else:
+    loc, s = torch.chunk(logits, 2, dim=-1)
+    scale = head_scale(s, policy.min_std)
+  if policy.deterministic or eps is None:
+    eps = torch.zeros_like(loc)
+  raw = loc + scale * eps.to(logits.dtype)
+  return torch.tanh(raw), raw, loc, scale
 
 
 class MLPPolicy:
@@ -209,16 +222,7 @@ class MLPPolicy:
     logits = x
     if self.head == 'identity':
       return logits, logits, torch.zeros(logits.shape[:-1], dtype=dt, device=logits.device), logits
-    if self._loc_only():
-      loc, scale = logits, torch.ones_like(logits)
-    else:
-      loc, s = torch.chunk(logits, 2, dim=-1)
-      scale = head_scale(s, self.min_std)
-    if self.deterministic or eps is None:
-      eps = torch.zeros_like(loc)
-    eps = eps.to(dt)
-    raw = loc + scale * eps
-    action = torch.tanh(raw)
+    action, raw, loc, scale = normal_tanh_head(self, logits, eps)
     return action, raw, normal_tanh_log_prob(loc, scale, raw).sum(-1), logits
 
   def descriptor(self, action_size):
@@ -251,14 +255,20 @@ def normal_slabs(out, slab_n, n_slabs, seed, offset, slab_stride):
 
 
 def _packed(state, dev):
-  qbuf = packed_buffer(state.qp)
-  if qbuf is None:
-    qbuf = torch.zeros(state.qp.pos.shape[:-1] + (16,), dtype=torch.float32, device=dev)
-    for lo, f in ((0, state.qp.pos), (3, state.qp.rot), (7, state.qp.vel), (10, state.qp.ang)):
-      qbuf[..., lo:lo + f.shape[-1]] = f
-  if qbuf.dtype != torch.float32 or qbuf.device != dev or not qbuf.is_contiguous():
-    qbuf = qbuf.to(dev, torch.float32).contiguous()
-  return qbuf
+  """`pack_qp` of a state's QP (the GPU tests read final states through it)."""
+  return pack_qp(state.qp, dev)
+
+
+def step_noise(policy, K, B, A, seed, offset, stride, dev):
+  """The chained paths' eps, step by step: yields K times one (B, A) buffer,
+  refilled for step t by one `bx_normal_slabs` launch at `offset + t *
+  stride`; zeros for a deterministic policy or an identity head (no draws)."""
+  eps = torch.zeros((B, A), dtype=torch.float32, device=dev)
+  draws = not policy.deterministic and policy.head == 'normal_tanh'
+  for t in range(K):
+    if draws:
+      normal_slabs(eps, B * A, 1, seed, offset + t * stride, 0)
+    yield eps
 
 
 def _extras(extras, K, B, A, dev):
@@ -295,12 +305,8 @@ def fused_supported(env, policy, trajectory: bool = True) -> Optional[str]:
     return f'the policy reads {policy.obs_size} observations, the env writes {u.obs_size}'
   if not trajectory:
     return None
-  p = u._params(opts, None, None)  # pylint: disable=protected-access
-  p.auto_reset = 0
-  lib = _native.lib()
-  rc = lib.bx_env_rollout_policy(u.sys._h, C.byref(p), 0, 0, None, None, None, None, None,  # pylint: disable=protected-access
-                                 C.byref(desc), 0, 0, 0, None, None, None, None, None, None)
-  return None if rc == 0 else lib.bx_last_error().decode()
+  return packed.refusal(u, opts, 'bx_env_rollout_policy', 0, 0, None, None, None, None, None,
+                        C.byref(desc), 0, 0, 0, None, None, None, None, None, None)
 
 
 def policy_rollout(env, state: State, policy: MLPPolicy, k: int, seed: int = 0, offset: int = 0,
@@ -334,35 +340,13 @@ def policy_rollout(env, state: State, policy: MLPPolicy, k: int, seed: int = 0, 
     return _chained(env, state, policy, int(k), seed, offset, step_stride)
   u, opts = chain_options(env)
   dev = u.sys.device
-  qbuf = _packed(state, dev)
+  qbuf = pack_qp(state.qp, dev)
   B, A, K = qbuf.shape[0], u.action_size, int(k)
   stride = 2 * B * A if step_stride is None else int(step_stride)
-  auto = bool(opts.get('auto_reset'))
-  info_in = state.info
-  first_qp = info_in.get('first_qp') if auto else None
-  first_obs = info_in.get('first_obs') if auto else None
-  if auto and (first_qp is None or first_obs is None):
-    raise ValueError('AutoResetWrapper state lacks first_qp / first_obs')
-  p = u._cached_params(opts, first_qp, first_obs)  # pylint: disable=protected-access
-  obs_in = _f32(state.obs, dev)
-  if not obs_in.is_contiguous():
-    obs_in = obs_in.contiguous()
-  if tuple(obs_in.shape) != (B, u.obs_size):
-    raise ValueError(f'state.obs {tuple(obs_in.shape)} != ({B}, {u.obs_size})')
-  done_in = _f32(state.done, dev)
-  steps_in = info_in.get('steps')
-  if steps_in is not None:
-    steps_in = _f32(steps_in, dev)
-  rng_in = info_in.get('rng')
-  if rng_in is None and getattr(u, 'needs_rng', False):
-    rng_in = torch.zeros((B,), dtype=torch.int32, device=dev)
-  N, O, M = u.sys.num_bodies, u.obs_size, len(u.metric_keys)
-  block = B * (N * 16 + O + 4 + M)
-  if out is None:
-    out = torch.empty((K * block,), dtype=torch.float32, device=dev)
-  elif (out.numel() < K * block or out.dtype != torch.float32 or not out.is_contiguous()
-        or out.device != dev):
-    raise ValueError(f'out must hold {K * block} contiguous float32 on {dev}')
+  p, done_in, steps_in, rng_in = packed.step_inputs(u, opts, state, B)
+  obs_in = packed.obs_input(u, state, B)
+  lay = packed.layout(u, B)
+  out = lay.out_buffer(out, K, dev)
   ex = _extras(extras, K, B, A, dev)
   rng_out = torch.empty((K, B), dtype=torch.int32, device=dev) if rng_in is not None else None
   desc = policy.descriptor(A)
@@ -372,28 +356,10 @@ def policy_rollout(env, state: State, policy: MLPPolicy, k: int, seed: int = 0, 
       None if rng_in is None else rng_in.data_ptr(), C.byref(desc), seed, offset, stride,
       ex.action.data_ptr(), ex.raw_action.data_ptr(), ex.log_prob.data_ptr(), out.data_ptr(),
       None if rng_out is None else rng_out.data_ptr(), _stream(dev.index)))
-  blocks = out[:K * block].view(K, block)
-  q, obs, sc, met = torch.split(blocks, (B * N * 16, B * O, 4 * B, B * M), dim=1)
-  q = q.view(K, B, N, 16)
-  obs = obs.view(K, B, O)
-  sc = sc.view(K, 4, B)
-  met = met.view(K, B, M)
-  traj = Trajectory(qp=q, obs=obs, reward=sc[:, 0], done=sc[:, 1], steps=sc[:, 2],
-                    truncation=sc[:, 3], metrics=met, metric_keys=tuple(u.metric_keys),
-                    rng=rng_out)
-  info = dict(info_in)
-  if p.episode_length > 0:
-    info['steps'] = sc[K - 1, 2]
-    info['truncation'] = sc[K - 1, 3]
-  if rng_out is not None:
-    info['rng'] = rng_out[K - 1]
-  keys = u.metric_keys
-  m_in = state.metrics
-  extra = m_in.carried(keys) if type(m_in) is _Metrics else {
-      kk: v for kk, v in m_in.items() if kk not in keys}
-  final = State(qp=PackedQP(q[K - 1]), obs=obs[K - 1], reward=sc[K - 1, 0], done=sc[K - 1, 1],
-                metrics=_Metrics(met[K - 1] if M else None, keys, extra), info=info)
-  return final, traj, ex
+  views = lay.views(out, K)
+  final = packed.final_state(u, p, state, tuple(v[K - 1] for v in views),
+                             None if rng_out is None else rng_out[K - 1])
+  return final, trajectory(u, views, rng_out), ex
 
 
 def _chained(env, state, policy, K, seed, offset, step_stride):
@@ -402,13 +368,9 @@ def _chained(env, state, policy, K, seed, offset, step_stride):
   B, A = state.obs.shape[0], env.action_size
   policy.for_actions(A)
   stride = 2 * B * A if step_stride is None else int(step_stride)
-  eps = torch.zeros((K, B, A), dtype=torch.float32, device=dev)
-  if not policy.deterministic and policy.head == 'normal_tanh':  # (an identity head draws none)
-    for t in range(K):
-      normal_slabs(eps[t], B * A, 1, seed, offset + t * stride, 0)
   acts, raws, lps, steps = [], [], [], []
-  for t in range(K):
-    a, r, lp, _ = policy.forward(state.obs.to(torch.float32), eps[t])
+  for eps in step_noise(policy, K, B, A, seed, offset, stride, dev):
+    a, r, lp, _ = policy.forward(state.obs.to(torch.float32), eps)
     state = env.step(state, a)
     acts.append(a)
     raws.append(r)
@@ -416,14 +378,6 @@ def _chained(env, state, policy, K, seed, offset, step_stride):
     steps.append(state)
   zeros = torch.zeros((B,), dtype=torch.float32, device=dev)
 
-  def qp16(s):
-    buf = packed_buffer(s.qp)
-    if buf is not None:
-      return buf
-    buf = torch.zeros(s.qp.pos.shape[:-1] + (16,), dtype=torch.float32, device=dev)
-    for lo, f in ((0, s.qp.pos), (3, s.qp.rot), (7, s.qp.vel), (10, s.qp.ang)):
-      buf[..., lo:lo + f.shape[-1]] = f
-    return buf
   try:
     keys = tuple(chain_options(env)[0].metric_keys)
   except NotImplementedError:
@@ -433,7 +387,7 @@ def _chained(env, state, policy, K, seed, offset, step_stride):
   rng = (torch.stack([s.info['rng'] for s in steps]) if steps[-1].info.get('rng') is not None
          else None)
   traj = Trajectory(
-      qp=torch.stack([qp16(s) for s in steps]), obs=torch.stack([s.obs for s in steps]),
+      qp=torch.stack([pack_qp(s.qp, dev) for s in steps]), obs=torch.stack([s.obs for s in steps]),
       reward=torch.stack([_f32(s.reward, dev) for s in steps]),
       done=torch.stack([_f32(s.done, dev) for s in steps]),
       steps=torch.stack([_f32(s.info.get('steps', zeros), dev) for s in steps]),

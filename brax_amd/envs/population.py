@@ -30,12 +30,13 @@ import numpy as np
 import torch
 
 from brax_amd import _native, abi
-from brax_amd.base import PackedQP
-from brax_amd.envs import wrappers
-from brax_amd.envs.env import State, _f32, _Metrics
-from brax_amd.envs.policy import (_ACTIVATIONS, MLPPolicy, _packed, _stream, fused_supported,
-                                  normal_slabs)
+from brax_amd.base import pack_qp
+from brax_amd.envs import packed, wrappers
+from brax_amd.envs.env import State, _f32
+from brax_amd.envs.policy import (_ACTIVATIONS, MLPPolicy, fused_supported, normal_slabs,
+                                  normal_tanh_head, step_noise)
 from brax_amd.envs.rollout import chain_options
+from brax_amd.system import _stream
 
 
 class PolicyPopulation:
@@ -242,19 +243,14 @@ def population_supported(env, population, param_stride: Optional[int] = None,
   if why is not None:
     return why
   u, opts = chain_options(inner)
-  p = u._params(opts, None, None)  # pylint: disable=protected-access
-  p.auto_reset = 0
   desc = policy.descriptor(u.action_size)
   if pop is not None:
     desc.params = pop.rows.data_ptr()
   stride = (0 if pop is None else pop.stride) if param_stride is None else int(param_stride)
   arg = abi.BxPopulation(param_stride=stride,
                          head=abi.HEADS[policy.head] if head is None else abi.HEADS.get(head, -1))
-  lib = _native.lib()
-  rc = lib.bx_env_eval_population(u.sys._h, C.byref(p), 0, 0, None, None, None, None, None,  # pylint: disable=protected-access
-                                  C.byref(desc), 0, 0, 0, None, None, None, None, C.byref(arg),
-                                  None)
-  return None if rc == 0 else lib.bx_last_error().decode()
+  return packed.refusal(u, opts, 'bx_env_eval_population', 0, 0, None, None, None, None, None,
+                        C.byref(desc), 0, 0, 0, None, None, None, None, C.byref(arg), None)
 
 
 def population_rollout(env, state: State, population, k: Optional[int] = None, seed: int = 0,
@@ -288,9 +284,9 @@ def population_rollout(env, state: State, population, k: Optional[int] = None, s
     stage: False reads the rows from global memory whatever the LDS budget
       (the same bits; None: the library's plan).
     out, eval_out, mom_out: optional buffers for the fused launch to write: a
-      flat contiguous float32 of B * (N*16 + O + 4 + M) floats, a contiguous
-      float32 (M + 3, B) and a contiguous float32 (B, 2 O + 1); the result's
-      tensors are views of them.
+      flat contiguous float32 of one block (`packed.Layout.block` floats), a
+      contiguous float32 (M + 3, B) and a contiguous float32 (B, 2 O + 1); the
+      result's tensors are views of them.
   Returns:
     (the state after the K-th step, the PopulationResult).
   """
@@ -316,31 +312,13 @@ def population_rollout(env, state: State, population, k: Optional[int] = None, s
     return _chained(inner, state, policy, pop, K, seed, offset, reward_shift, moments, carry)
   u, opts = chain_options(inner)
   dev = u.sys.device
-  qbuf = _packed(state, dev)
+  qbuf = pack_qp(state.qp, dev)
   A = u.action_size
-  auto = bool(opts.get('auto_reset'))
-  info_in = state.info
-  first_qp = info_in.get('first_qp') if auto else None
-  first_obs = info_in.get('first_obs') if auto else None
-  if auto and (first_qp is None or first_obs is None):
-    raise ValueError('AutoResetWrapper state lacks first_qp / first_obs')
-  p = u._cached_params(opts, first_qp, first_obs)  # pylint: disable=protected-access
-  done_in = _f32(state.done, dev)
-  steps_in = info_in.get('steps')
-  if steps_in is not None:
-    steps_in = _f32(steps_in, dev)
-  rng_in = info_in.get('rng')
-  if rng_in is None and getattr(u, 'needs_rng', False):
-    rng_in = torch.zeros((B,), dtype=torch.int32, device=dev)
+  p, done_in, steps_in, rng_in = packed.step_inputs(u, opts, state, B)
   keys = tuple(u.metric_keys)
-  N, O, M = u.sys.num_bodies, u.obs_size, len(keys)
-  obs_in = _f32(state.obs, dev)
-  if not obs_in.is_contiguous():
-    obs_in = obs_in.contiguous()
-  if tuple(obs_in.shape) != (B, O):
-    raise ValueError(f'state.obs {tuple(obs_in.shape)} != ({B}, {O})')
+  O, M = u.obs_size, len(keys)
+  obs_in = packed.obs_input(u, state, B)
   ev, mom = _fresh(carry, keys, B, O, moments, dev)
-  block = B * (N * 16 + O + 4 + M)
   for name, buf, shape in (('eval_out', eval_out, (M + 3, B)), ('mom_out', mom_out, (B, 2 * O + 1))):
     if buf is not None and (tuple(buf.shape) != shape or buf.dtype != torch.float32
                             or not buf.is_contiguous() or buf.device != dev):
@@ -349,11 +327,8 @@ def population_rollout(env, state: State, population, k: Optional[int] = None, s
     ev = eval_out.copy_(ev)
   if mom_out is not None and mom is not None:
     mom = mom_out.copy_(mom)
-  if out is None:
-    out = torch.empty((block,), dtype=torch.float32, device=dev)
-  elif (out.numel() < block or out.dtype != torch.float32 or not out.is_contiguous()
-        or out.device != dev):
-    raise ValueError(f'out must hold {block} contiguous float32 on {dev}')
+  lay = packed.layout(u, B)
+  out = lay.out_buffer(out, 1, dev)
   rng_out = torch.empty((B,), dtype=torch.int32, device=dev) if rng_in is not None else None
   ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
   desc = policy.descriptor(A)
@@ -366,19 +341,9 @@ def population_rollout(env, state: State, population, k: Optional[int] = None, s
       u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), obs_in.data_ptr(), done_in.data_ptr(),  # pylint: disable=protected-access
       ptr(steps_in), ptr(rng_in), C.byref(desc), int(seed), int(offset), 2 * B * A, ev.data_ptr(),
       out.data_ptr(), ev.data_ptr(), ptr(rng_out), C.byref(arg), _stream(dev.index)))
-  q, obs, sc, met = torch.split(out[:block], (B * N * 16, B * O, 4 * B, B * M))
-  sc = sc.view(4, B)
-  info = {kk: v for kk, v in info_in.items() if kk != 'eval_metrics'}
-  if p.episode_length > 0:
-    info['steps'] = sc[2]
-    info['truncation'] = sc[3]
-  if rng_out is not None:
-    info['rng'] = rng_out
-  m_in = state.metrics
-  extra = dict(m_in.carried(keys) if type(m_in) is _Metrics else {
-      kk: v for kk, v in m_in.items() if kk not in keys})
-  final = State(qp=PackedQP(q.view(B, N, 16)), obs=obs.view(B, O), reward=sc[0], done=sc[1],
-                metrics=_Metrics(met.view(B, M) if M else None, keys, extra), info=info)
+  final = packed.final_state(
+      u, p, state, lay.step_views(out[:lay.block]), rng_out,
+      info={kk: v for kk, v in state.info.items() if kk != 'eval_metrics'})
   return final, _result(ev, mom, keys, O, bool(arg.staged))
 
 
@@ -419,16 +384,7 @@ def forward_rows(policy: MLPPolicy, rows, obs, eps=None):
     if l + 1 < len(policy.sizes):
       x = fn(x)
     o += (i + 1) * n
-  if policy.head == 'identity':
-    return x
-  if policy._loc_only():  # pylint: disable=protected-access
-    loc, scale = x, torch.ones_like(x)
-  else:
-    loc, s = torch.chunk(x, 2, dim=-1)
-    scale = torch.nn.functional.softplus(s) + policy.min_std
-  if policy.deterministic or eps is None:
-    return torch.tanh(loc)
-  return torch.tanh(loc + scale * eps.to(dt))
+  return x if policy.head == 'identity' else normal_tanh_head(policy, x, eps)[0]
 
 
 def _chained(env, state, policy, pop, K, seed, offset, reward_shift, moments, carry):
@@ -444,12 +400,10 @@ def _chained(env, state, policy, pop, K, seed, offset, reward_shift, moments, ca
   M = len(keys)
   ev, mom = _fresh(carry, keys, B, O, moments, dev)
   rows = None if pop is None else pop.rows
-  stochastic = policy.head == 'normal_tanh' and not policy.deterministic
-  eps = torch.zeros((B, A), dtype=torch.float32, device=dev)
   shift = torch.tensor(float(reward_shift), dtype=torch.float32, device=dev)
   mean = None if policy.obs_mean is None else policy.obs_mean.to(dev)
   zeros = torch.zeros((B,), dtype=torch.float32, device=dev)
-  for t in range(K):
+  for eps in step_noise(policy, K, B, A, int(seed), int(offset), 2 * B * A, dev):
     obs = state.obs.to(torch.float32)
     active = ev[M + 1].clone()
     if mom is not None:
@@ -457,8 +411,6 @@ def _chained(env, state, policy, pop, K, seed, offset, reward_shift, moments, ca
       mom[:, :O] += active[:, None] * d
       mom[:, O:2 * O] += active[:, None] * (d * d)
       mom[:, 2 * O] += active
-    if stochastic:
-      normal_slabs(eps, B * A, 1, int(seed), int(offset) + t * 2 * B * A, 0)
     state = env.step(state, forward_rows(policy, rows, obs, eps))
     steps = _f32(state.info.get('steps', zeros), dev)
     ev[M + 2] = torch.where(active != 0, steps, ev[M + 2])

@@ -18,8 +18,10 @@ from typing import Any, Optional, Tuple
 import torch
 
 from brax_amd import _native
-from brax_amd.base import PackedQP, packed_buffer
-from brax_amd.envs.env import PhysicsEnv, State, Wrapper, _f32, _Metrics
+from brax_amd.base import pack_qp
+from brax_amd.envs import packed
+from brax_amd.envs.env import PhysicsEnv, State, Wrapper
+from brax_amd.envs.graph import _Captured
 from brax_amd.system import _stream
 
 
@@ -62,6 +64,13 @@ def chain_options(env):
   return w, opts
 
 
+def trajectory(u, views, rng) -> Trajectory:
+  """The Trajectory over `Layout.views` of the kernel env `u`'s K blocks."""
+  q, obs, reward, done, steps, trunc, met = views
+  return Trajectory(qp=q, obs=obs, reward=reward, done=done, steps=steps, truncation=trunc,
+                    metrics=met, metric_keys=tuple(u.metric_keys), rng=rng)
+
+
 def rollout(env, state: State, actions, out: Optional[torch.Tensor] = None
             ) -> Tuple[State, Trajectory]:
   """K consecutive `env.step(state, actions[t])` in one launch.
@@ -72,21 +81,15 @@ def rollout(env, state: State, actions, out: Optional[torch.Tensor] = None
     state: the state to start from (a batch of B envs).
     actions: (K, B, A) float32 on the env's device (any strides with a
       unit last-axis stride).
-    out: optional flat float32 buffer of K * B * (N*16 + O + 4 + M) floats
-      for the trajectory (reused across calls by graph captures).
+    out: optional flat float32 buffer of K blocks (`packed.Layout.block`
+      floats each) for the trajectory (reused across calls by graph captures).
   Returns:
     (the state after the K-th step, the Trajectory of all K steps); the
     state's tensors are views into the trajectory's last step.
   """
   u, opts = chain_options(env)
   dev = u.sys.device
-  qbuf = packed_buffer(state.qp)
-  if qbuf is None:
-    qbuf = torch.zeros(state.qp.pos.shape[:-1] + (16,), dtype=torch.float32, device=dev)
-    for lo, f in ((0, state.qp.pos), (3, state.qp.rot), (7, state.qp.vel), (10, state.qp.ang)):
-      qbuf[..., lo:lo + f.shape[-1]] = f
-  if qbuf.dtype != torch.float32 or qbuf.device != dev or not qbuf.is_contiguous():
-    qbuf = qbuf.to(dev, torch.float32).contiguous()
+  qbuf = pack_qp(state.qp, dev)
   B = qbuf.shape[0]
   act = actions
   if type(act) is not torch.Tensor or act.dtype != torch.float32 or act.device != dev:
@@ -96,27 +99,9 @@ def rollout(env, state: State, actions, out: Optional[torch.Tensor] = None
   if act.stride(-1) != 1:
     act = act.contiguous()
   K = act.shape[0]
-  auto = bool(opts.get('auto_reset'))
-  info_in = state.info
-  first_qp = info_in.get('first_qp') if auto else None
-  first_obs = info_in.get('first_obs') if auto else None
-  if auto and (first_qp is None or first_obs is None):
-    raise ValueError('AutoResetWrapper state lacks first_qp / first_obs')
-  p = u._cached_params(opts, first_qp, first_obs)  # pylint: disable=protected-access
-  done_in = _f32(state.done, dev)
-  steps_in = info_in.get('steps')
-  if steps_in is not None:
-    steps_in = _f32(steps_in, dev)
-  rng_in = info_in.get('rng')
-  if rng_in is None and getattr(u, 'needs_rng', False):
-    rng_in = torch.zeros((B,), dtype=torch.int32, device=dev)
-  N, O, M = u.sys.num_bodies, u.obs_size, len(u.metric_keys)
-  block = B * (N * 16 + O + 4 + M)
-  if out is None:
-    out = torch.empty((K * block,), dtype=torch.float32, device=dev)
-  elif (out.numel() < K * block or out.dtype != torch.float32 or not out.is_contiguous()
-        or out.device != dev):
-    raise ValueError(f'out must hold {K * block} contiguous float32 on {dev}')
+  p, done_in, steps_in, rng_in = packed.step_inputs(u, opts, state, B)
+  lay = packed.layout(u, B)
+  out = lay.out_buffer(out, K, dev)
   rng_out = torch.empty((K, B), dtype=torch.int32, device=dev) if rng_in is not None else None
   _native.check(_native.lib().bx_env_rollout_packed(
       u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), done_in.data_ptr(),  # pylint: disable=protected-access
@@ -124,31 +109,13 @@ def rollout(env, state: State, actions, out: Optional[torch.Tensor] = None
       None if rng_in is None else rng_in.data_ptr(), act.data_ptr(), act.stride(1),
       act.stride(0), act.shape[2], out.data_ptr(),
       None if rng_out is None else rng_out.data_ptr(), _stream(dev.index)))
-  blocks = out[:K * block].view(K, block)
-  q, obs, sc, met = torch.split(blocks, (B * N * 16, B * O, 4 * B, B * M), dim=1)
-  q = q.view(K, B, N, 16)
-  obs = obs.view(K, B, O)
-  sc = sc.view(K, 4, B)
-  met = met.view(K, B, M)
-  traj = Trajectory(qp=q, obs=obs, reward=sc[:, 0], done=sc[:, 1], steps=sc[:, 2],
-                    truncation=sc[:, 3], metrics=met, metric_keys=tuple(u.metric_keys),
-                    rng=rng_out)
-  info = dict(info_in)
-  if p.episode_length > 0:
-    info['steps'] = sc[K - 1, 2]
-    info['truncation'] = sc[K - 1, 3]
-  if rng_out is not None:
-    info['rng'] = rng_out[K - 1]
-  keys = u.metric_keys
-  m_in = state.metrics
-  extra = m_in.carried(keys) if type(m_in) is _Metrics else {
-      k: v for k, v in m_in.items() if k not in keys}
-  final = State(qp=PackedQP(q[K - 1]), obs=obs[K - 1], reward=sc[K - 1, 0], done=sc[K - 1, 1],
-                metrics=_Metrics(met[K - 1] if M else None, keys, extra), info=info)
-  return final, traj
+  views = lay.views(out, K)
+  final = packed.final_state(u, p, state, tuple(v[K - 1] for v in views),
+                             None if rng_out is None else rng_out[K - 1])
+  return final, trajectory(u, views, rng_out)
 
 
-class RolloutGraph:
+class RolloutGraph(_Captured):
   """`rollout` of K steps with on-device action draws, captured as one HIP
   graph: per replay ONE `bx_uniform_slabs` launch draws the K action slabs
   (slab t at `offset + (r * K + t) * step_stride`, the eager loop's
@@ -162,39 +129,16 @@ class RolloutGraph:
   def __init__(self, env, state: State, k: int, seed: int = 1, offset: int = 0,
                step_stride: Optional[int] = None, lo: float = -1.0, hi: float = 1.0,
                hook=None):
-    from brax_amd.envs.graph import _static  # pylint: disable=import-outside-toplevel
     if k < 1:
       raise ValueError(f'k must be >= 1, got {k}')
     u, _ = chain_options(env)
     dev = u.sys.device
     self.env, self.k, self.device = env, int(k), dev
-    buf = packed_buffer(state.qp)
-    B = (buf if buf is not None else state.qp.pos).shape[0]
+    B = self._static_inputs(u, state)
     A = env.action_size
     stride = B * A if step_stride is None else int(step_stride)
-    if buf is None:
-      buf = torch.zeros(state.qp.pos.shape[:-1] + (16,), dtype=torch.float32, device=dev)
-      for lo_, f in ((0, state.qp.pos), (3, state.qp.rot), (7, state.qp.vel), (10, state.qp.ang)):
-        buf[..., lo_:lo_ + f.shape[-1]] = f
-    self._qp = _static(buf)
-    self._done = _static(state.done)
-    info = dict(state.info)
-    self._steps = _static(info.get('steps'))
-    rng = info.get('rng')
-    if rng is None and getattr(u, 'needs_rng', False):
-      rng = torch.zeros((B,), dtype=torch.int32, device=dev)
-    self._rng = _static(rng)
-    if self._steps is not None:
-      info['steps'] = self._steps
-    if self._rng is not None:
-      info['rng'] = self._rng
-    self._in = State(qp=PackedQP(self._qp), obs=state.obs, reward=state.reward,
-                     done=self._done, metrics=state.metrics, info=info)
     self._acts = torch.empty((self.k, B, A), dtype=torch.float32, device=dev)
-    N, O, M = u.sys.num_bodies, u.obs_size, len(u.metric_keys)
-    self._out = torch.empty((self.k * B * (N * 16 + O + 4 + M),), dtype=torch.float32,
-                            device=dev)
-    self._epoch = torch.zeros((1,), dtype=torch.int64, device=dev)
+    self._out = packed.layout(u, B).out_buffer(None, self.k, dev)
     lib = _native.lib()
 
     def body(hook=hook):
@@ -204,30 +148,10 @@ class RolloutGraph:
       st, tr = rollout(env, self._in, self._acts, out=self._out)
       if hook is not None:
         hook(tr)
-      self._qp.copy_(packed_buffer(st.qp))
-      self._done.copy_(st.done)
-      if self._steps is not None:
-        self._steps.copy_(st.info['steps'])
-      if self._rng is not None:
-        self._rng.copy_(st.info['rng'])
-      self._epoch.add_(1)
+      self._feed_back(st)
       return st, tr
 
-    with torch.cuda.device(dev):
-      statics = [t for t in (self._qp, self._done, self._steps, self._rng) if t is not None]
-      snap = [t.clone() for t in statics]
-      side = torch.cuda.Stream(dev)
-      side.wait_stream(torch.cuda.current_stream(dev))
-      with torch.cuda.stream(side):
-        body(hook=None)
-      torch.cuda.current_stream(dev).wait_stream(side)
-      for dst, src in zip(statics, snap):
-        dst.copy_(src)
-      self._epoch.zero_()
-      self.graph = torch.cuda.CUDAGraph()
-      with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
-        self._res = body()
-      torch.cuda.current_stream(dev).synchronize()
+    self._res = self._capture(body)
 
   def replay(self):
     """Steps every env K steps forward; returns (state, trajectory)."""
@@ -258,41 +182,29 @@ class RolloutRunner:
     dev = u.sys.device
     self.env, self.k, self.device, self.hook = env, int(k), dev, hook
     self._u = u
-    buf = packed_buffer(state.qp)
-    B = (buf if buf is not None else state.qp.pos).shape[0]
-    A = env.action_size
+    qbuf = pack_qp(state.qp, dev)
+    B, A = qbuf.shape[0], env.action_size
     self.B, self.A = B, A
     self.seed, self.offset, self.lo, self.hi = seed, int(offset), float(lo), float(hi)
     self.stride = B * A if step_stride is None else int(step_stride)
-    N, O, M = u.sys.num_bodies, u.obs_size, len(u.metric_keys)
-    self.N, self.O, self.M = N, O, M
-    self.block = B * (N * 16 + O + 4 + M)
-    self._out = torch.empty((2, self.k * self.block), dtype=torch.float32, device=dev)
-    needs_rng = state.info.get('rng') is not None or getattr(u, 'needs_rng', False)
-    self._rng = torch.zeros((2, self.k, B), dtype=torch.int32, device=dev) if needs_rng else None
-    self._acts = torch.empty((self.k, B, A), dtype=torch.float32, device=dev)
-    auto = bool(opts.get('auto_reset'))
-    self._first = (state.info.get('first_qp'), state.info.get('first_obs')) if auto else (None, None)
-    if auto and None in self._first:
-      raise ValueError('AutoResetWrapper state lacks first_qp / first_obs')
-    self._p = u._params(opts, *self._first)  # pylint: disable=protected-access
+    self._start = state  # (it also keeps the auto-reset first state of `_p` alive)
+    self._p, done_in, steps_in, rng_in = packed.step_inputs(u, opts, state, B)
     self._has_steps = self._p.episode_length > 0
+    self._lay = packed.layout(u, B)
+    self._out = torch.empty((2, self.k * self._lay.block), dtype=torch.float32, device=dev)
+    self._rng = (torch.zeros((2, self.k, B), dtype=torch.int32, device=dev)
+                 if rng_in is not None else None)
+    self._acts = torch.empty((self.k, B, A), dtype=torch.float32, device=dev)
     # the starting state goes into buffer 1's last step: chunk 0 reads it there
-    last = self._views(1)
-    if buf is None:
-      for lo_, f in ((0, state.qp.pos), (3, state.qp.rot), (7, state.qp.vel), (10, state.qp.ang)):
-        last['qp'][..., lo_:lo_ + f.shape[-1]] = f
+    q, _, _, done, steps, _, _ = self._last(1)
+    q.copy_(qbuf)
+    done.copy_(done_in)
+    if steps_in is not None:
+      steps.copy_(steps_in)
     else:
-      last['qp'].copy_(buf)
-    last['done'].copy_(torch.as_tensor(state.done, dtype=torch.float32, device=dev))
-    if state.info.get('steps') is not None:
-      last['steps'].copy_(torch.as_tensor(state.info['steps'], dtype=torch.float32, device=dev))
-    else:
-      last['steps'].zero_()
-    if self._rng is not None and state.info.get('rng') is not None:
-      self._rng[1, self.k - 1].copy_(state.info['rng'])
-    self._metrics_in = state.metrics
-    self._info_in = dict(state.info)
+      steps.zero_()
+    if rng_in is not None:
+      self._rng[1, self.k - 1].copy_(rng_in)
     self._c = 0
     self._cur = 1  # the buffer holding the latest trajectory
     self._lib = _native.lib()
@@ -307,28 +219,24 @@ class RolloutRunner:
     self._args = {}
     self._stream_key = None
 
-  def _views(self, i):
-    K, B, N, O, M = self.k, self.B, self.N, self.O, self.M
-    blk = self._out[i].view(K, self.block)[K - 1]
-    q, obs, sc, met = torch.split(blk, (B * N * 16, B * O, 4 * B, B * M))
-    sc = sc.view(4, B)
-    return {'qp': q.view(B, N, 16), 'obs': obs.view(B, O), 'reward': sc[0], 'done': sc[1],
-            'steps': sc[2], 'truncation': sc[3], 'metrics': met.view(B, M)}
+  def _last(self, i):
+    """The views of buffer i's last step."""
+    return self._lay.step_views(self._out[i].view(self.k, self._lay.block)[self.k - 1])
 
   def _launch_args(self, src, stream):
     """(the arguments before the draw offset, the ones after it) of the
     launch that reads buffer `src` and writes the other, on `stream`."""
     dst = 1 - src
-    K, B, N, O = self.k, self.B, self.N, self.O
-    base = self._out[src].data_ptr() + 4 * (K - 1) * self.block
-    sc = base + 4 * B * (N * 16 + O)
+    K, B, lay = self.k, self.B, self._lay
+    base = self._out[src].data_ptr() + 4 * (K - 1) * lay.block  # the last step's qp
+    done_in = base + 4 * lay.offset['done']
+    steps_in = base + 4 * lay.offset['steps'] if self._has_steps else None
     rng_in = None if self._rng is None else self._rng[src, K - 1].data_ptr()
     rng_out = None if self._rng is None else self._rng[dst].data_ptr()
-    steps_in = sc + 8 * B if self._has_steps else None
     vp = C.c_void_p
     h = self._u.sys._h  # pylint: disable=protected-access
     if self.draw:
-      pre = (h, C.byref(self._p), C.c_int64(B), C.c_int32(K), vp(base), vp(sc + 4 * B),
+      pre = (h, C.byref(self._p), C.c_int64(B), C.c_int32(K), vp(base), vp(done_in),
              vp(steps_in), vp(rng_in), C.c_uint64(self.seed))
       post = (C.c_uint64(self.stride), C.c_float(self.lo), C.c_float(self.hi),
               C.c_int64(self.A), vp(self._acts.data_ptr()), vp(self._out[dst].data_ptr()),
@@ -338,7 +246,7 @@ class RolloutRunner:
              C.c_uint64(self.seed))
       post = ((C.c_uint64(self.stride), None, C.c_uint64(0), C.c_float(self.lo),
                C.c_float(self.hi), stream),
-              (h, C.byref(self._p), C.c_int64(B), C.c_int32(K), vp(base), vp(sc + 4 * B),
+              (h, C.byref(self._p), C.c_int64(B), C.c_int32(K), vp(base), vp(done_in),
                vp(steps_in), vp(rng_in), vp(self._acts.data_ptr()), C.c_int64(self.A),
                C.c_int64(B * self.A), C.c_int64(self.A), vp(self._out[dst].data_ptr()),
                vp(rng_out), stream))
@@ -371,27 +279,11 @@ class RolloutRunner:
     return self._acts
 
   def trajectory(self) -> Trajectory:
-    K, B, N, O, M = self.k, self.B, self.N, self.O, self.M
-    blocks = self._out[self._cur].view(K, self.block)
-    q, obs, sc, met = torch.split(blocks, (B * N * 16, B * O, 4 * B, B * M), dim=1)
-    sc = sc.view(K, 4, B)
-    return Trajectory(qp=q.view(K, B, N, 16), obs=obs.view(K, B, O), reward=sc[:, 0],
-                      done=sc[:, 1], steps=sc[:, 2], truncation=sc[:, 3],
-                      metrics=met.view(K, B, M), metric_keys=tuple(self._u.metric_keys),
-                      rng=None if self._rng is None else self._rng[self._cur])
+    return trajectory(self._u, self._lay.views(self._out[self._cur], self.k),
+                      None if self._rng is None else self._rng[self._cur])
 
   def state(self) -> State:
     """The state after the last run (views of the current trajectory)."""
-    v = self._views(self._cur)
-    info = dict(self._info_in)
-    if self._has_steps:
-      info['steps'] = v['steps']
-      info['truncation'] = v['truncation']
-    if self._rng is not None:
-      info['rng'] = self._rng[self._cur, self.k - 1]
-    keys = self._u.metric_keys
-    m_in = self._metrics_in
-    extra = m_in.carried(keys) if type(m_in) is _Metrics else {
-        k: v_ for k, v_ in m_in.items() if k not in keys}
-    return State(qp=PackedQP(v['qp']), obs=v['obs'], reward=v['reward'], done=v['done'],
-                 metrics=_Metrics(v['metrics'] if self.M else None, keys, extra), info=info)
+    return packed.final_state(
+        self._u, self._p, self._start, self._last(self._cur),
+        None if self._rng is None else self._rng[self._cur, self.k - 1])
