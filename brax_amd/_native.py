@@ -102,6 +102,8 @@ _SIGS = {
     'bx_mlp_forward': abi.SIGNATURES['bx_mlp_forward'],
     'bx_mlp_backward': abi.SIGNATURES['bx_mlp_backward'],
     'bx_ppo_head': abi.SIGNATURES['bx_ppo_head'],
+    'bx_opt_sizes': abi.SIGNATURES['bx_opt_sizes'],
+    'bx_adam_step': abi.SIGNATURES['bx_adam_step'],
 }
 
 EXPORTS = tuple(_SIGS)

@@ -217,6 +217,21 @@ PPO_HEAD_ARGS = (
     ('normalize_advantage', C.c_int), ('losses', _vp), ('dlogits', _seq), ('dbaseline', _seq),
     ('vs', _seq), ('advantages', _seq), ('workspace', _vp),
     ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
+OPT_MAX_TENSORS = 32  # BX_OPT_MAX_TENSORS
+OPT_CHUNK = 1024  # elements of one tensor that one workgroup of bx_adam_step owns
+
+
+class BxOptTensor(C.Structure):
+  """One tensor of bx_adam_step's table: n contiguous float32 at each of p, g,
+  m, v (and target, None for no target update)."""
+  _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p),
+              ('target', C.c_void_p), ('n', C.c_int64), ('lr', C.c_float), ('tau', C.c_float)]
+
+
+OPT_SIZES_ARGS = (('tensor_bytes', C.POINTER(C.c_int32)),)
+ADAM_STEP_ARGS = (
+    ('t', C.POINTER(BxOptTensor)), ('n_tensors', C.c_int32), ('step', C.c_int64),
+    ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_float), ('stream', _vp))
 PLAN_FIELDS = ('mode', 'lanes', 'lds_bytes', 'feat', 'gw', 'fold', 'jb', 'cb')  # bx_system_blob
 SYSTEM_BLOB_ARGS = (
     ('desc', _vp), ('reset', _vp), ('words', C.POINTER(C.c_uint32)), ('capacity', C.c_int64),
@@ -228,7 +243,8 @@ ARGS = {'bx_system_blob': SYSTEM_BLOB_ARGS,
         'bx_population_delta': POPULATION_DELTA_ARGS,
         'bx_replay_insert': REPLAY_INSERT_ARGS, 'bx_replay_sample': REPLAY_SAMPLE_ARGS,
         'bx_mlp_sizes': MLP_SIZES_ARGS, 'bx_mlp_forward': MLP_FORWARD_ARGS,
-        'bx_mlp_backward': MLP_BACKWARD_ARGS, 'bx_ppo_head': PPO_HEAD_ARGS}
+        'bx_mlp_backward': MLP_BACKWARD_ARGS, 'bx_ppo_head': PPO_HEAD_ARGS,
+        'bx_opt_sizes': OPT_SIZES_ARGS, 'bx_adam_step': ADAM_STEP_ARGS}
 SIGNATURES = {name: ([t for _, t in args], C.c_int) for name, args in ARGS.items()}
 
 

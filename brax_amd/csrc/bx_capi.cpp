@@ -11,6 +11,7 @@
 #include "../../include/brax_amd.h"
 #include "bx_blob.h"
 #include "mlp_launch.h"
+#include "optim_launch.h"
 #include "ppo_head_launch.h"
 #include "pbd_features.h"
 #include "pbd_launch.h"
@@ -1362,6 +1363,61 @@ int bx_ppo_head(int64_t n_steps, int64_t n_envs, int64_t n_actions, const bx_seq
   a.adv = *advantages;
   ppo_head_carve(a, workspace);
   HIP_OK(launch_ppo_head(a, st));
+  return 0;
+}
+
+int bx_opt_sizes(int32_t* tensor_bytes) {
+  if (!tensor_bytes) return fail("null argument");
+  *tensor_bytes = (int32_t)sizeof(bx_opt_tensor);
+  return 0;
+}
+
+int bx_adam_step(const bx_opt_tensor* t, int32_t n_tensors, int64_t step, double beta1,
+                 double beta2, float eps, void* stream) {
+  if (!t) return fail("null tensor table");
+  if (n_tensors < 1 || n_tensors > BX_OPT_MAX_TENSORS)
+    return fail("n_tensors " + std::to_string(n_tensors) + " outside 1.." +
+                std::to_string(BX_OPT_MAX_TENSORS));
+  if (step < 1) return fail("step must be >= 1 (the count after this step)");
+  // (the range checks and the double arithmetic live in optim_kernels.hip,
+  // whose flags keep NaN comparisons and IEEE division; this unit's do not)
+  if (const char* why = opt_check_scalars(beta1, beta2, eps)) return fail(why);
+  OptArgs a{};
+  int64_t groups = 0;
+  int k = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    const bx_opt_tensor& s = t[i];
+    if (s.n < 0) return fail("tensor " + std::to_string(i) + ": negative n");
+    if (s.n == 0) continue;
+    if (!s.p || !s.g || !s.m || !s.v)
+      return fail("tensor " + std::to_string(i) + ": null p, g, m or v");
+    OptTensor& d = a.t[k];
+    d.p = s.p;
+    d.g = s.g;
+    d.m = s.m;
+    d.v = s.v;
+    d.target = s.target;
+    d.n = s.n;
+    opt_set_tensor(d, s.lr, s.tau, step, beta1);
+    const uintptr_t bits = (uintptr_t)s.p | (uintptr_t)s.g | (uintptr_t)s.m | (uintptr_t)s.v |
+                           (uintptr_t)s.target;
+    d.vec = (bits & 15) == 0;
+    a.first[k] = (int32_t)groups;
+    groups += opt_chunks(s.n);
+    if (groups > (int64_t)0x7fffffff) return fail("too many elements for one launch");
+    ++k;
+  }
+  if (k == 0) return 0;
+  a.first[k] = (int32_t)groups;
+  a.n_tensors = k;
+  opt_set_scalars(a, step, beta1, beta2, eps);
+  int dev = -1;
+  hipStream_t st = as_stream(stream);
+  if (st) HIP_OK(hipStreamGetDevice(st, &dev));
+  else HIP_OK(hipGetDevice(&dev));
+  DeviceScope scope(dev);
+  if (scope.err != hipSuccess) return fail(std::string("device: ") + hipGetErrorString(scope.err));
+  HIP_OK(launch_adam_step(a, st));
   return 0;
 }
 

@@ -27,6 +27,7 @@ from brax_amd.envs.evaluator import Evaluator
 from brax_amd.envs.policy import MLPPolicy, policy_rollout
 from brax_amd.envs.population import update_running_statistics
 from brax_amd.training import networks as ppo_networks
+from brax_amd.training import optim
 from brax_amd.training.losses import Transition, ppo_loss
 from brax_amd.training.ppo_head import METRICS
 
@@ -107,6 +108,20 @@ def _detached(layers):
   return [(w.detach(), b.detach()) for w, b in layers]
 
 
+def make_optimizer(params, learning_rate: float, fused_adam=False):
+  """Adam over `params`: `torch.optim.Adam` (`fused_adam` False), or
+  `optim.FusedAdam`, one launch per step (True: that or NotImplementedError;
+  None: that where it applies). Both have `zero_grad` and `step`."""
+  if fused_adam is not False:
+    groups = [dict(params=params, lr=learning_rate)]
+    why = optim.supported(groups)
+    if why is None:
+      return optim.FusedAdam(groups, eps=1e-8)
+    if fused_adam is True:
+      raise NotImplementedError(f'no fused Adam: {why}')
+  return torch.optim.Adam(params, lr=learning_rate, eps=1e-8)
+
+
 class Learner:
   """The state of one PPO run and the three phases of a training step."""
 
@@ -117,7 +132,7 @@ class Learner:
                normalize_observations: bool = False, normalize_advantage: bool = True,
                seed: int = 0, network_factory=ppo_networks.make_ppo_networks, device=None,
                fused_gae: Optional[bool] = None, action_repeat: int = 1, fused_mlp=False,
-               fused_head=False):
+               fused_head=False, fused_adam=False):
     assert batch_size * num_minibatches % num_envs == 0
     self.env, self.device = env, torch.device(device)
     self.action_repeat = int(action_repeat)
@@ -126,7 +141,7 @@ class Learner:
     self.num_updates_per_batch = int(num_updates_per_batch)
     self.unrolls = batch_size * num_minibatches // num_envs
     self.seed, self.fused_gae, self.fused_mlp = int(seed), fused_gae, fused_mlp
-    self.fused_head = fused_head
+    self.fused_head, self.fused_adam = fused_head, fused_adam
     self.loss_kwargs = dict(entropy_cost=entropy_cost, discounting=discounting,
                             reward_scaling=reward_scaling, gae_lambda=gae_lambda,
                             clipping_epsilon=clipping_epsilon,
@@ -135,8 +150,8 @@ class Learner:
     self.policy_layers, self.value_layers = network_factory(O, A, seed=seed, device=self.device)
     self.normalizer = RunningStatistics(O, self.device) if normalize_observations else None
     # optax.adam's defaults (eps 1e-8, as torch's)
-    self.optimizer = torch.optim.Adam(
-        ppo_networks.parameters(self.policy_layers, self.value_layers), lr=learning_rate, eps=1e-8)
+    self.optimizer = make_optimizer(
+        ppo_networks.parameters(self.policy_layers, self.value_layers), learning_rate, fused_adam)
     self.actor = self.make_policy(self.params)
     self._gen = torch.Generator(device=self.device).manual_seed(self.seed)
     self._noise_offset = 0
@@ -240,7 +255,7 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
           deterministic_eval: bool = False, network_factory=ppo_networks.make_ppo_networks,
           progress_fn: Callable[[int, dict], None] = lambda *args: None,
           normalize_advantage: bool = True, eval_env=None, device=None,
-          fused_gae: Optional[bool] = None, fused_mlp=False, fused_head=False):
+          fused_gae: Optional[bool] = None, fused_mlp=False, fused_head=False, fused_adam=False):
   """PPO training; the reference's arguments and defaults
   (`ppo/train.py:61-86`).
 
@@ -259,6 +274,9 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
       chained torch; True: `bx_ppo_head` or NotImplementedError; None: the
       kernel where it applies); where the kernel is taken it runs its own GAE
       scan and `fused_gae` is not consulted.
+    fused_adam: the optimiser (False: `torch.optim.Adam`; True:
+      `optim.FusedAdam`, one launch per Adam step, or NotImplementedError; None:
+      `FusedAdam` where it applies).
   Returns:
     `(make_policy, params, metrics)`: `make_policy(params, deterministic=False)`
     gives an `MLPPolicy`; `params` is (the normaliser or None, the policy
@@ -287,7 +305,8 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
                     normalize_observations=normalize_observations,
                     normalize_advantage=normalize_advantage, seed=seed,
                     network_factory=network_factory, device=dev, fused_gae=fused_gae,
-                    action_repeat=action_repeat, fused_mlp=fused_mlp, fused_head=fused_head)
+                    action_repeat=action_repeat, fused_mlp=fused_mlp, fused_head=fused_head,
+                    fused_adam=fused_adam)
   key = np.array([0, int(seed)], np.uint32)  # jax.random.PRNGKey(seed) layout
   key_env, key_eval = wrappers.split_key(key)
   learner.reset(key_env)

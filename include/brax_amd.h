@@ -938,6 +938,66 @@ int bx_ppo_head(int64_t n_steps, int64_t n_envs, int64_t n_actions, const bx_seq
                 void* workspace, int64_t* workspace_bytes, void* stream);
 
 /*
+ * The fused optimiser step: torch.optim.Adam's update (its default path: no
+ * weight decay, no amsgrad, not maximising) of up to BX_OPT_MAX_TENSORS
+ * float32 tensors, and the soft update of a target copy of those that have
+ * one, in ONE launch on `stream`. Tensor k is n contiguous floats at each of
+ * p (the parameter), g (its gradient, read only), m and v (the first and
+ * second moments); the arrays of the table must not overlap.
+ *
+ * `step` >= 1 is the step count AFTER this step, as torch has it. The betas
+ * are doubles because 1 - beta is formed from them: 1 - (float)0.999 is off
+ * 0.001 by 1.3e-5 of it, a hundred float32 ulps of every v. The host forms, in
+ * double, narrowed to float32 once:
+ *   w1      = (float)(1 - beta1)         w2 = (float)(1 - beta2)
+ *   b2      = (float)beta2
+ *   c2      = (float)sqrt(1 - beta2^step)
+ *   s_k     = (float)(lr_k / (1 - beta1^step))
+ *   u_k     = (float)(1 - tau_k)
+ * and the kernel does, per element, every operation rounded to float32 on its
+ * own (no contraction, no pow, IEEE division and square root):
+ *   m      = m + (g - m) * w1
+ *   v      = v * b2 + (g * g) * w2
+ *   denom  = sqrt(v) / c2 + eps
+ *   p      = p - s_k * (m / denom)
+ * and then, where target != NULL, in the same lane on the same element
+ *   target = target * u_k + p * tau_k        (p the value just written)
+ * which are the bits of `t * (1 - tau) + q * tau` as three float32 tensor
+ * operations. NaN and Inf propagate as IEEE has them; the step is elementwise,
+ * so a non-finite gradient element reaches no other element.
+ *
+ * A workgroup of 256 lanes owns 1024 consecutive elements of one tensor; the
+ * table and the prefix sums of the tensors' workgroup counts travel in the
+ * kernel's arguments, so a call allocates nothing, copies nothing, does not
+ * synchronise, may be captured into a graph, and may name other gradient
+ * pointers on every call. (`step` is a host value: a captured call replays
+ * that step's bias corrections.) A tensor whose p, g, m, v and target are all
+ * 16-byte aligned moves in 16-byte accesses, any other a float at a time with
+ * the same results; no lane touches an element at or past n.
+ *
+ * A null table, n_tensors outside 1..BX_OPT_MAX_TENSORS, step < 1, a negative
+ * n, a null p, g, m or v on a tensor with n > 0, a beta outside [0, 1) (NaN
+ * included), eps < 0 (or NaN), or more than 2^31 - 1 workgroups fail before
+ * any device call. Tensors with n = 0 are skipped and a table of only such
+ * tensors launches nothing. No system handle: the launch goes to the device
+ * that owns `stream` (the current device for NULL). bx_opt_sizes writes
+ * sizeof(bx_opt_tensor) as compiled. (Additive: no ABI bump.) */
+#define BX_OPT_MAX_TENSORS 32
+typedef struct bx_opt_tensor {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;      /* n floats each */
+  float* target; /* NULL: no target update */
+  int64_t n;
+  float lr;
+  float tau;
+} bx_opt_tensor;
+int bx_opt_sizes(int32_t* tensor_bytes);
+int bx_adam_step(const bx_opt_tensor* t, int32_t n_tensors, int64_t step, double beta1,
+                 double beta2, float eps, void* stream);
+
+/*
  * Standalone HBM-streaming phase kernels over a structure-of-arrays batch
  * (the integrator and collider phases benchmarked in isolation).
  * SoA: field plane k, body b, env e at base[k*plane + b*n_envs + e]; the 13
