@@ -4104,10 +4104,13 @@ __device__ __forceinline__ constexpr bool ek_has(int k) {
 #define KIND_IS(k) (ek_has<EK>(k) && kind == (k))
 
 // counter-based uniform: splitmix64 of (seed, global index) -> [lo, hi)
-__device__ __forceinline__ float uniform_at(uint64_t seed, uint64_t i, float lo, float hi) {
-  const uint64_t z = mix64(seed, i);
+// (uniform_of: from the mixed word, for a caller that carries the counter)
+__device__ __forceinline__ float uniform_of(uint64_t z, float lo, float hi) {
   float u = (float)(z >> 40) * (1.0f / 16777216.0f);
   return lo + (hi - lo) * u;
+}
+__device__ __forceinline__ float uniform_at(uint64_t seed, uint64_t i, float lo, float hi) {
+  return uniform_of(mix64(seed, i), lo, hi);
 }
 
 // the arm tip of the reachers: body coef[1]'s (.11, 0, 0) in the world and
@@ -4512,6 +4515,53 @@ __device__ void env_observe(const Cst& c, const BlobHdr& H, const Env& E, int la
     obs_out[i] = obs_elem<EK>(c, H, E, kind, flags, i, act, aw, act != nullptr, coef);
 }
 
+// RT (env_step_body): what the open-loop Ant rollout kernel keeps of a
+// launch's output addresses. Step t's outputs are one packed block, so every
+// address is the block's base plus a byte offset that depends on the lane
+// alone: the base is uniform and advances by the block once per step, the
+// offsets are formed once per launch. (32-bit offsets: the kernel runs at one
+// wave per SIMD at most, pbd_dispatch.h ant_wide, so a block is a few MB.)
+struct RollTail {
+  char* blk;   // this step's output block
+  char* arec;  // this step's recorded action rows (draws with act_out)
+  uint32_t q;    // the lane's body record
+  uint32_t row;  // the env's observation row, element `lane`
+  uint32_t ot, oj, ov, oc, oa;  // obs: torso scalar, joint angle / velocity, contact vel / ang
+  uint32_t sc, met, act;        // reward (done, steps, truncation: + 4 B each), metrics, action
+  const float* tsrc;            // the torso scalar's word in LDS
+  bool ton;                     // the lane writes a torso scalar
+};
+__device__ __forceinline__ float* tail_at(char* base, uint32_t off) {
+  // (opaque here, so the zero-extension stays at the access and the address
+  // is the instruction's own base + 32-bit offset form: hoisted out of the
+  // step loop it becomes a 64-bit pair and an add per access)
+  asm volatile("" : "+v"(off));
+  return reinterpret_cast<float*>(base + off);
+}
+// the Ant branch of env_observe's stores (the same words to the same
+// elements), every lane's source and destination from RollTail
+template <int L>
+__device__ __forceinline__ void ant_observe_store(const BlobHdr& H, const Env& E, int lane,
+                                                  const RollTail& T, bool forces) {
+  const int N = H.N, D = H.D;
+  if (T.ton) *tail_at(T.blk, T.ot) = *T.tsrc;
+  for (int j = lane, o = 0; j < D; j += L, o += 4 * L) {
+    *tail_at(T.blk, T.oj + o) = E.ang[j];
+    *tail_at(T.blk, T.ov + o) = E.ang[D + j];
+  }
+  if (forces)
+    for (int b = lane, o = 0; b < N; b += L, o += 12 * L) {
+      const float* a = E.acc + b * ACC_STRIDE;
+      float* ov = tail_at(T.blk, T.oc + o);
+      float* oa = tail_at(T.blk, T.oa + o);
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        ov[k] = clip1(a[ACC_ICV + k]);
+        oa[k] = clip1(a[ACC_ICA + k]);
+      }
+    }
+}
+
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
@@ -4821,13 +4871,22 @@ __device__ __forceinline__ float* policy_eval(const PolArgs& Q, const float* W, 
 // lane's contact row stays in registers over the launch (FrozenB), read
 // after the state is in LDS and again after a step in which the lane's env
 // took AutoReset's first_qp
+// RT (env_rollout_kernel of the Ant kind alone, not its wide twin): the
+// per-step tail on RollTail's running addresses. The step index forms no
+// address: the output block's base, the recorded actions' base, the draw's
+// counter and the given actions' row advance by their step strides at the end
+// of a step, and the observation places its elements by per-lane offsets
+// formed once per launch. Indices only: every stored word is the one the
+// other kernels store
 template <int L, int MODE, int F, int M, int EK = EK_ANY, bool PK = false, bool ONE = false,
-          bool POL = false, bool EVL = false, bool POP = false, bool ZH = true>
+          bool POL = false, bool EVL = false, bool POP = false, bool ZH = true, bool RT = false>
 __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q = PolArgs{},
                                               const EvalArgs& V = EvalArgs{},
                                               const PopArgs& N = PopArgs{}) {
   static_assert(!EVL || (PK && !ONE), "the evaluation kernels run on the packed K-step layout");
   static_assert(!POP || (POL && EVL), "the population kernels are evaluation kernels with a policy");
+  static_assert(!RT || (PK && !ONE && !POL && !EVL && MODE == MODE_SINGLE && EK == EK_ANT && L == 16),
+                "the running tail is the open-loop Ant rollout kernel's");
   BX_KSTAMP_DECL
   extern __shared__ __attribute__((aligned(16))) float smem[];
   // the packed SINGLE-mode kernels (Env.step's bx_env_step_packed, the
@@ -4922,6 +4981,35 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   };
   const float* arow_g = drw ? nullptr : A.act + el * A.act_stride;
   float a0 = 0.f;
+  // RT: the lane's draw counter before the mix (step 0's; + draw_step per
+  // step) and the launch's output addresses
+  uint64_t dz = 0;
+  RollTail T{};
+  if constexpr (RT) {
+    const int lc = lane < aw ? lane : aw - 1;
+    dz = mix64_start(A.draw_seed, A.draw_offset + (uint64_t)el * (uint64_t)aw + (uint64_t)lc);
+    const int N = H.N, D = H.D, O = P.obs_size;
+    const int x = (P.obs_flags & BX_OBS_XY) ? 2 : 0;
+    const uint32_t Bn = (uint32_t)A.n_envs, en = (uint32_t)el;
+    T.blk = reinterpret_cast<char*>(A.out.qp.pos.ptr);
+    T.arec = reinterpret_cast<char*>(A.act_out);
+    T.q = 4u * ((en * N + (lane < N ? lane : 0)) * 16);
+    const uint32_t orow = Bn * N * 16 + en * O;
+    T.row = 4u * (orow + lane);
+    // (x, y,) z, rot 4 | vel 3, ang 3: lane l's scalar and where it goes
+    const int k = lane - x;
+    T.ton = lane < x + 11;
+    T.tsrc = E.qp + (lane < x ? lane : (k < 5 ? 2 + k : 7 + (k - 5)));
+    T.ot = 4u * (orow + (k < 5 ? lane : x + 5 + D + (k - 5)));
+    T.oj = 4u * (orow + x + 5 + lane);
+    T.ov = 4u * (orow + x + 11 + D + lane);
+    T.oc = 4u * (orow + x + 11 + 2 * D + 3 * lane);
+    T.oa = T.oc + 4u * (3 * N);
+    const uint32_t osc = Bn * (N * 16 + O);
+    T.sc = 4u * (osc + en);
+    T.met = 4u * (osc + 4 * Bn + en * P.n_metrics);
+    T.act = 4u * (en * aw + lane);
+  }
   // POL: the staged parameters, the env's observation row and activation
   // buffers (past every env's area)
   const float* pw = nullptr;
@@ -5049,6 +5137,14 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   if constexpr (POL) {
     pact = policy_eval<L, POP>(Q, pw, pobs, pb0, pb1, lane, el, e, valid, t, aw, A.n_envs, POP ? N.head : 0);
     esync<L>();
+  } else if (RT && t > 0) {
+    if (drw) {
+      dz += A.draw_step;
+      if (aw > 0 && lane < C) a0 = uniform_of(mix64_finish(dz), A.draw_lo, A.draw_hi);
+    } else {
+      arow_g += A.act_step;
+      if (aw > 0 && lane < C) a0 = arow_g[lane < aw ? lane : aw - 1];
+    }
   } else if (t > 0) {
     if (drw) {
       if (aw > 0 && lane < C) a0 = draw_at(t, lane < aw ? lane : aw - 1);
@@ -5060,7 +5156,10 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   // this step's outputs
   bx_env_state O;
   float* blk = nullptr;  // PK: this step's output block
-  if constexpr (PK) {
+  if constexpr (RT) {
+    // (T's addresses; the Ant kind has no per-env stream)
+    O = bx_env_state{};
+  } else if constexpr (PK) {
     const int64_t B = A.n_envs;
     blk = EVL ? A.out.qp.pos.ptr : A.out.qp.pos.ptr + t * A.out_step;
     O.obs = blk + B * H.N * 16;
@@ -5085,7 +5184,8 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   // body b's output record
   auto store_out_qp = [&](int b, const float* src) {
     if constexpr (PK) {
-      float* d = blk + (e * H.N + b) * 16;  // dword-aligned at any batch
+      // (RT: b is the lane, N <= L)
+      float* d = RT ? tail_at(T.blk, T.q) : blk + (e * H.N + b) * 16;  // dword-aligned at any batch
       st4a(d, f32x4{src[0], src[1], src[2], src[3]});
       st4a(d + 4, f32x4{src[4], src[5], src[6], src[7]});
       st4a(d + 8, f32x4{src[8], src[9], src[10], src[11]});
@@ -5107,7 +5207,9 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
     } else if (i0 > 0 && lane < C)
       v = drw ? draw_at(t, i < aw ? i : aw - 1) : ((EARLY && i0 == C) ? ea1 : arow_g[i < aw ? i : aw - 1]);
     if (i >= aw || !valid) v = 0.f;
-    if (drw && A.act_out && valid && lane < C && i < aw) A.act_out[((int64_t)t * A.n_envs + e) * aw + i] = v;
+    if constexpr (RT) {
+      if (drw && A.act_out && valid && lane < C && i < aw) *tail_at(T.arec, T.act + 4 * i0) = v;
+    } else if (drw && A.act_out && valid && lane < C && i < aw) A.act_out[((int64_t)t * A.n_envs + e) * aw + i] = v;
     if constexpr (EK == EK_ANT && L == 16) {
       // the Ant kernel: the squares summed across the env's 16 lanes by DPP
       // (a butterfly order instead of lane 0's serial one)
@@ -5237,8 +5339,11 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
     // (its launch requires fold), so its observation takes the lane's
     // hoisted body, joint and actuator
     env_observe<L, EK>(c, H, E, lane, kind, P.obs_flags, P.obs_size, act, aw,
-                   (valid && (POL || last)) ? (POL ? pobs : O.obs + e * P.obs_size) : nullptr, P.coef, S ? &X.J : nullptr,
+                   (!RT && valid && (POL || last)) ? (POL ? pobs : O.obs + e * P.obs_size) : nullptr, P.coef, S ? &X.J : nullptr,
                    (S && !JBK) ? &X.B : nullptr, (S && EK == EK_HUM) ? &X.A : nullptr);
+    // (RT: env_observe left the angles in LDS; the row from the lane's offsets)
+    if constexpr (RT)
+      if (valid) ant_observe_store<L>(H, E, lane, T, P.coef[7] != 0.f);
     BX_KSTAMP(12);
     // the Ant kernel's contact cost: each body lane's clipped squares, summed
     // across the env's lanes by DPP
@@ -5250,7 +5355,9 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
     // reward / done / metrics (lane 0 of the env)
     if (lane == 0 && valid) {
       const float dt = H.dt;
-      float* m = EVL ? (P.n_metrics > 0 ? em : nullptr) : (O.metrics ? O.metrics + e * P.n_metrics : nullptr);
+      float* m = EVL ? (P.n_metrics > 0 ? em : nullptr)
+                 : RT ? (P.n_metrics > 0 ? tail_at(T.blk, T.met) : nullptr)
+                      : (O.metrics ? O.metrics + e * P.n_metrics : nullptr);
       v3 p1 = ld3(E.qp);
       float reward = 0.f;
       if (KIND_IS(BX_ENV_ANT)) {
@@ -5468,7 +5575,16 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   }
   if (P.auto_reset) reset_now = done != 0.f;
   if (valid) {
-    if (lane == 0 && last) {
+    if constexpr (RT) {
+      // reward | done | steps | truncation, B words apart
+      if (lane == 0) {
+        const uint32_t B4 = 4u * (uint32_t)A.n_envs;
+        *tail_at(T.blk, T.sc) = reward_sum;
+        *tail_at(T.blk, T.sc + B4) = done;
+        *tail_at(T.blk, T.sc + 2 * B4) = steps;
+        *tail_at(T.blk, T.sc + 3 * B4) = trunc;
+      }
+    } else if (lane == 0 && last) {
       O.reward[e] = reward_sum;
       O.done[e] = done;
       if (O.steps) O.steps[e] = steps;
@@ -5512,6 +5628,10 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
       }
       for (int i = lane; i < P.obs_size; i += L) {
         const float fo = P.first_obs[e * P.obs_size + i];
+        if constexpr (RT) {
+          *tail_at(T.blk, T.row + 4 * (i - lane)) = fo;
+          continue;
+        }
         if (last) O.obs[e * P.obs_size + i] = fo;
         if constexpr (POL) pobs[i] = fo;
       }
@@ -5525,6 +5645,10 @@ __device__ __forceinline__ void env_step_body(const EnvArgs& A, const PolArgs& Q
   done_in = done;
   steps_in = steps;
   rng_c += (uint32_t)reps;
+  if constexpr (RT) {
+    T.blk += 4 * A.out_step;
+    T.arec += 4 * A.n_envs * aw;
+  }
   esync<L>();
   if constexpr (CBH) {
     // the env's records are first_qp's now, its frozen bodies' among them

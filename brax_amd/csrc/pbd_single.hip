@@ -38,10 +38,12 @@ env_rollout_wide_kernel(EnvArgs A) {
 }
 // the same body under its own name for multi-step launches of the
 // benchmarked envs' kernels (bx_env_rollout_packed), so a profile tells
-// K-step launches from single steps
+// K-step launches from single steps; the Ant kind's with the per-step tail on
+// running addresses (env_step_body's RT)
 template <int L, int MODE, int F, int M, int EK = EK_ANY>
 __global__ void __launch_bounds__(L > 64 ? L : 64) BX_STEP_ATTR env_rollout_kernel(EnvArgs A) {
-  env_step_body<L, MODE, F, M, EK, true>(A);
+  constexpr bool RT = EK == EK_ANT && L == 16 && MODE == MODE_SINGLE;
+  env_step_body<L, MODE, F, M, EK, true, false, false, false, false, true, RT>(A);
 }
 
 // the system step: the variant's kernel (generated from the variant list,
