@@ -44,6 +44,26 @@ struct bx_system : bx::Plan {
   uint32_t* blob = nullptr;
   float* movf = nullptr;  // MULTI: the penetrating contacts past MCBUF, per env (grown on demand)
   int64_t movf_envs = 0;
+  // the overflow buffers that growth superseded: an earlier launch or a graph
+  // captured at a smaller batch may still hold them, so they live until destroy
+  std::vector<float*> movf_old;
+
+  // frees every overflow buffer, the current one and the superseded ones
+  hipError_t free_movf() {
+    hipError_t e = hipSuccess;
+    for (float* p : movf_old) {
+      hipError_t f = hipFree(p);
+      if (e == hipSuccess) e = f;
+    }
+    movf_old.clear();
+    if (movf) {
+      hipError_t f = hipFree(movf);
+      if (e == hipSuccess) e = f;
+    }
+    movf = nullptr;
+    movf_envs = 0;
+    return e;
+  }
 };
 
 namespace {
@@ -212,6 +232,7 @@ int bx_system_create(const bx_desc* desc, const bx_reset_desc* reset, int device
   if (e == hipSuccess) e = hipMemcpy(S->blob, S->words.data(), S->words.size() * 4, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     std::string m = std::string("device setup: ") + hipGetErrorString(e);
+    (void)S->free_movf();
     if (S->blob) (void)hipFree(S->blob);
     delete S;
     return fail(m);
@@ -222,9 +243,9 @@ int bx_system_create(const bx_desc* desc, const bx_reset_desc* reset, int device
 
 int bx_system_destroy(bx_system* S) {
   if (!S) return 0;
-  if (S->blob || S->movf) {
+  if (S->blob || S->movf || !S->movf_old.empty()) {
     DEVICE_SCOPE(S);
-    if (S->movf) HIP_OK(hipFree(S->movf));
+    HIP_OK(S->free_movf());
     if (S->blob) HIP_OK(hipFree(S->blob));
   }
   delete S;
@@ -340,16 +361,21 @@ int bx_system_step(bx_system* S, int64_t n_envs, const bx_qp* qin, const float* 
   if (info) a.info = *info;
   if (S->mode == 3 && S->hdr.R > MCBUF && S->movf_envs < n_envs) {
     // the overflow contacts (a pass with more than MCBUF penetrating rows):
-    // grown to this batch once; a capture cannot allocate
+    // grown to this batch once; a capture cannot allocate. The buffer is
+    // scratch, written before it is read within a step, so growth copies
+    // nothing and waits for nothing: the new allocation serves this launch and
+    // the later ones, and the superseded one is kept until bx_system_destroy,
+    // because launches in flight and graphs captured at the smaller batch hold
+    // its address. Batches that double keep at most about twice the largest
+    // buffer; nothing ever shrinks.
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     HIP_OK(hipStreamIsCapturing(as_stream(stream), &cs));
     if (cs != hipStreamCaptureStatusNone)
       return fail("MULTI overflow buffer: step the batch once before capturing it");
-    HIP_OK(hipStreamSynchronize(as_stream(stream)));
-    if (S->movf) HIP_OK(hipFree(S->movf));
-    S->movf = nullptr;
-    S->movf_envs = 0;
-    HIP_OK(hipMalloc(&S->movf, (size_t)n_envs * (S->hdr.R - MCBUF) * MOVF_W * 4));
+    float* grown = nullptr;
+    HIP_OK(hipMalloc(&grown, (size_t)n_envs * (S->hdr.R - MCBUF) * MOVF_W * 4));
+    if (S->movf) S->movf_old.push_back(S->movf);
+    S->movf = grown;
     S->movf_envs = n_envs;
   }
   a.movf = S->movf;

@@ -24,6 +24,7 @@ of one per step (`draw='per_step'` keeps the per-step launch).
 from typing import Callable, Optional
 
 import ctypes as C
+import gc
 import torch
 
 from brax_amd import _native
@@ -95,6 +96,11 @@ class _Captured:
       for dst, src in zip(statics, snap):
         dst.copy_(src)
       self._epoch.zero_()
+      # a dead System waits in a reference cycle (System <-> JointGroup) for
+      # the cyclic collector, and its finaliser frees device memory: were the
+      # collector to run inside the capture, that hipFree would invalidate it
+      # (torch.cuda.graph no longer collects on entry by default)
+      gc.collect()
       self.graph = torch.cuda.CUDAGraph()
       # thread_local: only this thread's calls are checked during capture, so
       # a process group's watchdog thread polling its collectives' events (the

@@ -356,7 +356,13 @@ int bx_system_set_block(bx_system* sys, int threads);
  * act: (B, act_width) with row stride act_stride (0 broadcasts one row).
  * Action indices are clipped to [0, act_width) like the reference's
  * `jp.take(act, index)` (jumpy.py:146-151); act_width >= 1 unless the system
- * reads no action. qp_in and qp_out may not alias. info may be NULL. */
+ * reads no action. qp_in and qp_out may not alias. info may be NULL.
+ * A MULTI system's overflow buffer (the penetrating contacts past the first
+ * 128 of a pass) is scratch, written before it is read within a step, and
+ * every allocation of it lives as long as the System, so a graph captured at
+ * one batch stays valid after later steps at larger ones. Stepping one System
+ * concurrently on two streams is unsupported: both calls would use the same
+ * per-env slices of that buffer. */
 int bx_system_step(bx_system* sys, int64_t n_envs, const bx_qp* qp_in,
                    const float* act, int64_t act_stride, int64_t act_width,
                    const bx_qp* qp_out, const bx_info* info, void* stream);

@@ -326,7 +326,7 @@ def _bits(qp, info):
 @pytest.mark.parametrize('cutoff', CUTOFFS)
 def test_overflow_buffer_slices_and_growth(dev, scene, cutoff, variant):
   """A fresh System steps envs [:3] (the overflow buffer sized for 3), then
-  all 64 (the buffer is freed and reallocated, after a stream synchronise),
+  all 64 (the buffer grows: a new allocation, the old one kept until destroy),
   then [:3] again (three slices of the larger buffer): both 3-env results are
   the first three rows of the 64-env result bit for bit, state and Info;
   the 64 stepped twice give identical bits; every env lists more than MCBUF
