@@ -1,5 +1,5 @@
 // bx_blob.h — the host blob builder: descriptor -> the device blob's words and
-// the kernel plan (mode, lanes, features, LDS). Plain C++17, no HIP: bx_capi.cpp
+// the kernel plan (mode, lanes, features, LDS). Plain C++17, no HIP: bx_capi_system.cpp
 // copies the words to the device and launches by the plan.
 #pragma once
 #include <stddef.h>

@@ -3,7 +3,7 @@ the inputs a launch reads from a `State`, and the `State` it returns.
 
 `bx_env_step_packed` and the K-step entry points built on it (`rollout`,
 `policy_rollout`, `eval_rollout`, `population_rollout`, `RolloutRunner`) write
-one block of float32 words per step (`bx_capi.cpp`, `env_step_packed`):
+one block of float32 words per step (`bx_capi_env.cpp`, `env_step_packed`):
 
     qp (B, N, 16) | obs (B, O) | reward, done, steps, truncation (B,) each |
     metrics (B, M)
