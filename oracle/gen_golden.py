@@ -294,9 +294,14 @@ def qp_unpack(a):
 # trajectories
 # ---------------------------------------------------------------------------
 
-def env_traj(env, name, n_envs, n_steps, act_seed_base=10_000):
-  """Unwrapped env: reset from seeds 0..B-1, then T random-action steps."""
+def env_traj(env, name, n_envs, n_steps, act_seed_base=10_000, qp0=None):
+  """Unwrapped env: reset from seeds 0..B-1, then T random-action steps.
+  `qp0`: a list of per-env start states (n_envs of (N, 13) arrays); each
+  env's State is its reset State with `qp` replaced, so `qp[0]` is the start
+  state while `obs[0]`, `reset_obs`, `reset_qpos` and `reset_qvel` stay the
+  reset's."""
   A = env.action_size
+  label, name = name, name[len('mid_'):] if name.startswith('mid_') else name
   out = {k: [] for k in ('qp', 'obs', 'reward', 'done', 'metrics', 'info_contact',
                          'info_actuator', 'contact_pos', 'contact_normal',
                          'contact_penetration')}
@@ -333,6 +338,9 @@ def env_traj(env, name, n_envs, n_steps, act_seed_base=10_000):
       qpos_l.append(env.sys.default_angle() + jp.random_uniform(r1, (D,), -.01, .01))
       qvel_l.append(jp.random_uniform(r2, (D,), -.01, .01))
     states.append(env.reset(rng))
+  if qp0 is not None:
+    assert len(qp0) == n_envs
+    states = [s.replace(qp=qp_unpack(q)) for s, q in zip(states, qp0)]
   acts = np.stack([np.random.default_rng(act_seed_base + t).uniform(-1, 1, (n_envs, A))
                    for t in range(n_steps)])
   metric_keys = sorted(states[0].metrics.keys())
@@ -374,7 +382,7 @@ def env_traj(env, name, n_envs, n_steps, act_seed_base=10_000):
     out['contact_pos'].append(np.stack([i.contact_pos for i in infos]))
     out['contact_normal'].append(np.stack([i.contact_normal for i in infos]))
     out['contact_penetration'].append(np.stack([i.contact_penetration for i in infos]))
-    print(f'  {name}: step {t + 1}/{n_steps}  ({time.time() - t0:.1f}s)', flush=True)
+    print(f'  {label}: step {t + 1}/{n_steps}  ({time.time() - t0:.1f}s)', flush=True)
   res = {k: np.stack(v) for k, v in out.items() if v}
   res['action'] = acts
   if qpos_l:
@@ -872,6 +880,36 @@ def _short_scenes():
           'box_slide_s': (scenes.BOX_TEST_CONFIG, 1, 10, None)}
 
 
+# mid-episode fixtures (oracle/mid_states.py): 8 envs, 2 steps, recorded by
+# the reference from start states the float64 C oracle picked
+MID = ['pusher', 'halfcheetah', 'hopper', 'walker2d', 'humanoidstandup', 'grasp']
+
+
+def mid_traj(name):
+  """`mid_<name>`: the env-layer rollout (the keys of traj_* / envtraj_*)
+  from the picked start states, plus `row_target` (the contact rows the
+  fixture exists for) and `comment`."""
+  from brax import envs
+  # this directory is on the path (`oracle` is oracle/oracle.py here); the
+  # repository root after it, for `tests.helpers` and `brax_amd`
+  if os.path.dirname(HERE) not in sys.path:
+    sys.path.append(os.path.dirname(HERE))
+  import mid_states
+  import oracle as oracle_lib
+  t0 = time.time()
+  starts, comment = mid_states.select(oracle_lib, name)
+  t1 = time.time()
+  env = envs.get_environment(name)
+  r = env_traj(env, 'mid_' + name, len(starts), mid_states.T,
+               act_seed_base=mid_states.ACT_SEED, qp0=list(starts))
+  assert np.array_equal(r['action'], mid_states.actions(env.action_size, len(starts)))
+  r['row_target'] = np.asarray(mid_states.TARGET[name], np.int32)
+  r['comment'] = np.array(comment)
+  print(f'  mid_{name}: start states {t1 - t0:.1f}s, reference rollout {time.time() - t1:.1f}s',
+        flush=True)
+  return r
+
+
 TORCH_ENVS = ['hopper', 'walker2d', 'inverted_pendulum', 'inverted_double_pendulum',
               'swimmer', 'reacher', 'reacherangle', 'acrobot', 'pusher', 'ur5e', 'grasp', 'fetch']
 
@@ -962,6 +1000,9 @@ def main():
     if want('env_' + name):
       env = envs.get_environment(name)
       save(f'envtraj_{name}', env_traj(env, name, 8, 4))
+  for name in MID:
+    if want('mid_' + name) and not args.desc_only:
+      save('mid_' + name, mid_traj(name))
   if want('wrap'):
     save('wrap_ant', wrapped_ant())
   if want('wrap_ar2'):

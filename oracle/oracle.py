@@ -115,6 +115,15 @@ class Oracle:
     self._fn('oracle_system_info')(C.byref(self.cdesc), C.c_int64(B), _p(qp), _p(ic))
     return ic
 
+  def joint_angles(self, qp):
+    """Every joint's limited angles (B, J, 3), zero past the joint's dof: the
+    angles the joint limits (`desc['joint_limit']`, (J, 3, 2)) clip."""
+    qp = self._a(qp)
+    B = qp.shape[0]
+    out = np.zeros((B, len(self.desc['joint_type']), 3), self.dtype)
+    self._fn('oracle_joint_angles')(C.byref(self.cdesc), C.c_int64(B), _p(qp), _p(out))
+    return out
+
   @staticmethod
   def _coef(coef):
     if coef is None:

@@ -1955,6 +1955,27 @@ static int angle_vel(const sysc* s, const body_t* qp, R* angles, R* vels) {
   return n;
 }
 
+/* Every joint's limited angles (`axis_angle`: the angles joint_apply_one and
+ * the spring limit clip against joint_limit), (B, J, 3), zero past the
+ * joint's dof: the goldens' joint-limit census (tests/test_golden_coverage.py) */
+int FN(oracle_joint_angles)(const bx_desc* d, int64_t B, const R* qp, R* angles) {
+  sysc s;
+  sys_init(&s, d);
+  int N = s.N, J = s.J;
+  body_t* q = calloc(N > 0 ? N : 1, sizeof(body_t));
+  for (int64_t e = 0; e < B; e++) {
+    load_qp(q, qp + e * 13 * N, N);
+    for (int j = 0; j < J; j++) {
+      R axes[3][3], ang[3] = {0, 0, 0};
+      int dof = axis_angle(&s, j, &q[d->joint_body_p[j]], &q[d->joint_body_c[j]], axes, ang);
+      for (int l = 0; l < 3; l++) angles[(e * J + j) * 3 + l] = l < dof ? ang[l] : (R)0;
+    }
+  }
+  free(q);
+  sys_free(&s);
+  return J;
+}
+
 static R clip1(R x) { return clip(x, -1, 1); }
 
 /* Ant._get_obs (ant.py:257-282), use_contact_forces=True -> 87 */

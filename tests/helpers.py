@@ -1,4 +1,6 @@
 """Shared test helpers: systems by name and the parity gate."""
+import os
+
 import numpy as np
 
 from brax_amd import compiler
@@ -89,6 +91,7 @@ def env_coef(name):
 
 def prep_oracle(o, name):
   """Per-env oracle state: Grasp's action map."""
+  name = env_kind(name) if name else name
   if name == 'grasp':
     from brax_amd.envs import tasks
     o.set_act_map(tasks.grasp_act_map(config_for(name)))
@@ -105,13 +108,34 @@ def golden_reset_qp(name, o, T):
   return qp0
 
 
+# mid-episode fixtures (oracle/gen_golden.py MID): env-layer rollouts of 2
+# steps from states the float64 oracle reached by seeded burn-in (Pusher: by a
+# seeded search over `object` placements), chosen so that the contact rows
+# `row_target` penetrate; one file serves the system and the env gates
+MID = ['mid_pusher', 'mid_halfcheetah', 'mid_hopper', 'mid_walker2d', 'mid_humanoidstandup']
+# Grasp's env step moves the palm and maps the action before System.step
+# (grasp.py:73-87), so its env-layer fixture's actions are not System.step's:
+# it serves the env gate only
+MID_ENV = ['mid_grasp']
+
+
 def env_golden(name):
   """Golden file of a kernel env's reference rollout."""
+  if name.startswith('mid_'):
+    return name
   return ('envtraj_' if name in ENVTRAJ_KERNEL else 'traj_') + name
 
 
+def sys_golden(name):
+  """Golden file of a system's reference System.step rollout."""
+  return name if name.startswith('mid_') else 'traj_' + name
+
+
 def env_kind(name):
-  """Env-layer kind of a golden name ('ant_spring', 'ant_xy' -> 'ant')."""
+  """Env-layer kind of a golden name ('ant_spring', 'ant_xy', 'mid_ant' ->
+  'ant')."""
+  if name.startswith('mid_'):
+    name = name[len('mid_'):]
   for suf in ('_spring', '_xy'):
     if name.endswith(suf):
       return name[:-len(suf)]
@@ -132,6 +156,8 @@ XCOL = ['heightmap', 'clipped', 'box_capsule', 'mesh_capsule', 'box_box', 'box_c
 
 
 def config_for(name):
+  if name.startswith('mid_'):
+    name = name[len('mid_'):]
   if name in SHORT_SCENES:
     base = name[:-2]
     cfg = config_for('box_ground' if base.startswith('box') else base)
@@ -246,6 +272,13 @@ def normwise(a, b):
   return err / scale
 
 
+WIDE = 1e-2  # a sample whose own bound 2 x E32 exceeds this is ill-conditioned
+NEAR_TOL = 1e-3  # the ill-conditioned envs: floor of the nearest-realisation bound
+# fp32-ulp perturbed copies per oracle build in the envelope:
+# 2 builds x (1 exact + 32 perturbed) = 66 realisations per env, so a
+# per-env E32_i is not a noisy maximum of a handful of runs
+N_PERTURB = int(os.environ.get('BX_ENVELOPE_N', '32'))
+
 QP_FIELDS = {'pos': slice(0, 3), 'rot': slice(3, 7), 'vel': slice(7, 10), 'ang': slice(10, 13)}
 
 
@@ -305,3 +338,30 @@ def normal_ref(seed, idx, dtype=np.float64):
   out = r * c
   assert out.dtype == np.dtype(dtype)
   return out
+
+
+class Envelope:
+  """Brax's algorithm in fp32 on the exact inputs and on ulp-perturbed
+  copies, in two oracle builds: plain float32 and float32 with a*b+c
+  contracted to fused multiply-adds (XLA's jit contracts them, as hipcc does);
+  the envelope is the max normwise error over every run."""
+
+  def __init__(self, oracle_lib, name, n_perturb=None, desc=None):
+    d, rd = desc if desc is not None else compiled(name)[1:3]
+    self.os = [prep_oracle(oracle_lib.Oracle(d, rd, np.float32, safe_guard=True, fma=f), name)
+               for f in (False, True)]
+    self.n = N_PERTURB if n_perturb is None else n_perturb
+
+  def _inputs(self, qp):
+    yield qp.astype(np.float32)
+    rng = np.random.default_rng(1234)
+    for _ in range(self.n):
+      noise = 1 + rng.uniform(-6e-8, 6e-8, qp.shape)
+      yield (qp * noise).astype(np.float32)
+
+  def system(self, qp, act):
+    return [o.system_step(q, act.astype(np.float32)) for o in self.os for q in self._inputs(qp)]
+
+  def env(self, name, qp, act, O, M, flags=0, coef=None):
+    return [o.env_step(name, q, act.astype(np.float32), O, M, obs_flags=flags, coef=coef)
+            for o in self.os for q in self._inputs(qp)]

@@ -283,3 +283,32 @@ def test_graph_capture_and_in_place_weights(dev):
   _, tr_n, ex_n = policy_rollout(env, st0, policy, K, seed=6, fused=True)
   assert torch.equal(got[0], ex_n.action) and torch.equal(got[1], ex_n.log_prob)
   assert torch.equal(got[2][..., :13], tr_n.qp[..., :13])
+
+
+@pytest.mark.parametrize('name', ['pusher', 'halfcheetah'])
+def test_fused_policy_rollout_from_contact_states(dev, oracle_lib, name):
+  """The fused policy kernel from the mid-episode fixtures' start states
+  (contact rows at work, tests/golden/mid_<name>.npz) with one small MLP:
+  the teacher-forced policy check, the open-loop kernel's bits on the
+  recorded actions, and the target rows penetrate inside the trajectory."""
+  from brax_amd.envs.policy import policy_rollout
+  from tests.test_gpu_rollout import contact_start, target_rows_penetrate
+  env, st0, acts, T = contact_start(name, dev)
+  B, K = acts.shape[1], 3
+  st0 = st0.replace(obs=env.observe(st0.qp, torch.zeros((B, env.action_size), device=dev)))
+  policy = _policy(env, dev, (32, 32))
+  seed, offset = 5, 1000
+  final, tr, ex = policy_rollout(env, st0, policy, K, seed=seed, offset=offset, fused=True)
+  torch.cuda.synchronize()
+  assert torch.isfinite(ex.action).all() and torch.isfinite(tr.obs).all()
+  eps = _eps(dev, K, B, env.action_size, seed, offset)
+  _check_policy(policy, st0, tr, ex, eps, f'{name}/mid')
+  _check_physics(env, st0, tr, ex)
+  # the policy's actions are not the fixture's, so the set of rows may differ
+  # from the recorded one: at least half of the fixture's active target rows
+  # penetrate in the closed-loop trajectory (HalfCheetah: its one row, on at
+  # least 4 envs)
+  from tests.test_gpu_rollout import fixture_rows
+  rows, envs = target_rows_penetrate(oracle_lib, name, T, st0, tr, ex.action)
+  assert 2 * len(rows & fixture_rows(T)) >= len(fixture_rows(T)), (rows, fixture_rows(T))
+  assert name != 'halfcheetah' or envs[0] >= 4, envs

@@ -229,3 +229,61 @@ def test_strided_autoreset_target(dev):
     a, b = env.step(a, acts[t]), env.step(b, acts[t])
     assert torch.equal(a.qp.pos, b.qp.pos) and torch.equal(a.obs, b.obs)
     assert torch.equal(a.done, b.done)
+
+
+def contact_start(name, dev, extra_seed=7):
+  """The mid-episode fixture of `name` (tests/golden/mid_<name>.npz): the bare
+  env, a State on the fixture's start states, and K = 3 actions: the
+  fixture's 2 recorded ones and one seeded draw after them."""
+  from brax_amd import envs
+  from brax_amd.base import qp_from_numpy
+  from brax_amd.envs.env import State
+  from tests.conftest import golden
+  T = golden('mid_' + name)
+  env = envs.get_environment(name, device=dev)
+  B = T['qp'].shape[1]
+  st0 = State(qp=qp_from_numpy(T['qp'][0], dev), obs=None, reward=torch.zeros(B, device=dev),
+              done=torch.zeros(B, device=dev))
+  last = np.random.default_rng(extra_seed).uniform(-1, 1, T['action'].shape[1:])
+  acts = torch.as_tensor(np.concatenate([T['action'], last[None]]), dtype=torch.float32, device=dev)
+  return env, st0, acts, T
+
+
+def target_rows_penetrate(oracle_lib, name, T, st0, tr, acts):
+  """(rows, envs per row): the fixture's target rows that penetrate at some
+  step of the GPU trajectory `tr`, and on how many envs each does: the
+  float64 oracle's Info on the states the steps started from (the start
+  state, then the kernel's own recorded states)."""
+  from tests.helpers import compiled
+  _, d, rd, _ = compiled(name)
+  o64 = oracle_lib.Oracle(d, rd, np.float64)
+  q0 = torch.cat([st0.qp.pos, st0.qp.rot, st0.qp.vel, st0.qp.ang], -1)
+  ins = [q0] + [tr.qp[t][..., :13] for t in range(acts.shape[0] - 1)]
+  hit = 0
+  for q, a in zip(ins, acts):
+    pen = o64.system_step(q.cpu().numpy(), a.cpu().numpy())[1]['contact_penetration']
+    hit = hit | (pen[:, T['row_target']] > 0)
+  return set(T['row_target'][hit.any(0)].tolist()), hit.sum(0)[hit.any(0)].tolist()
+
+
+def fixture_rows(T):
+  """The target rows that penetrate in the recorded fixture itself."""
+  tr = T['row_target']
+  return set(tr[(T['contact_penetration'][..., tr] > 0).any((0, 1))].tolist())
+
+
+@pytest.mark.parametrize('name', ['pusher', 'halfcheetah'])
+def test_rollout_from_contact_states(dev, oracle_lib, name):
+  """The K-step kernel from states whose contact rows are at work (the
+  mid-episode fixtures: Pusher's arm - object capsule pairs, HalfCheetah's
+  foot - foot pair), not from `reset`: every field bit-identical to chained
+  `env.step`, and the target rows penetrate inside the trajectory."""
+  env, st0, acts, T = contact_start(name, dev)
+  tr = _check(env, st0, acts)
+  torch.cuda.synchronize()
+  # the first two steps are the fixture's own: every target row the fixture
+  # has active penetrates in the kernel's trajectory too (HalfCheetah: its one
+  # row on at least 4 envs)
+  rows, envs = target_rows_penetrate(oracle_lib, name, T, st0, tr, acts)
+  assert rows == fixture_rows(T), (rows, fixture_rows(T))
+  assert name != 'halfcheetah' or envs[0] >= 4, envs
