@@ -102,6 +102,10 @@ _SIGS = {
     'bx_mlp_forward': abi.SIGNATURES['bx_mlp_forward'],
     'bx_mlp_backward': abi.SIGNATURES['bx_mlp_backward'],
     'bx_ppo_head': abi.SIGNATURES['bx_ppo_head'],
+    'bx_sac_head_prep': abi.SIGNATURES['bx_sac_head_prep'],
+    'bx_sac_head_sample': abi.SIGNATURES['bx_sac_head_sample'],
+    'bx_sac_head_losses': abi.SIGNATURES['bx_sac_head_losses'],
+    'bx_sac_head_sample_backward': abi.SIGNATURES['bx_sac_head_sample_backward'],
     'bx_opt_sizes': abi.SIGNATURES['bx_opt_sizes'],
     'bx_adam_step': abi.SIGNATURES['bx_adam_step'],
 }

@@ -217,6 +217,53 @@ PPO_HEAD_ARGS = (
     ('normalize_advantage', C.c_int), ('losses', _vp), ('dlogits', _seq), ('dbaseline', _seq),
     ('vs', _seq), ('advantages', _seq), ('workspace', _vp),
     ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
+# bx_sac_head_*: the SAC loss heads, one entry point per launch
+SAC_MAX_CRITICS, SAC_MAX_JOBS = 4, 3  # BX_SAC_MAX_CRITICS / BX_SAC_MAX_JOBS
+SAC_HEAD_BLOCK = 256  # rows of a workgroup
+SAC_HEAD_PART = 3  # doubles a workgroup of the losses launch leaves
+
+
+class BxSacSampleJob(C.Structure):
+  """One sample of bx_sac_head_sample: logits (B, 2A) and eps (B, A) in, action
+  (B, A) (None: not wanted) and log_prob (B,) out; pitches in elements."""
+  _fields_ = [('logits', C.c_void_p), ('logits_pitch', C.c_int64), ('eps', C.c_void_p),
+              ('eps_pitch', C.c_int64), ('action', C.c_void_p), ('action_pitch', C.c_int64),
+              ('log_prob', C.c_void_p)]
+
+
+class BxSacQ(C.Structure):
+  """The critics' outputs and their gradients for bx_sac_head_losses: C
+  contiguous (B,) arrays each."""
+  _fields_ = [(n, C.c_void_p * SAC_MAX_CRITICS)
+              for n in ('q_old', 'next_q', 'q_pi', 'dq_old', 'dq_pi')]
+
+
+class BxSacDaction(C.Structure):
+  """The action columns of each critic's input gradient, (B, A) at a pitch."""
+  _fields_ = [('ptr', C.c_void_p * SAC_MAX_CRITICS), ('pitch', C.c_int64 * SAC_MAX_CRITICS)]
+
+
+SAC_HEAD_PREP_ARGS = (
+    ('n_rows', C.c_int64), ('n_obs', C.c_int64), ('n_actions', C.c_int64), ('obs', _vp),
+    ('obs_pitch', C.c_int64), ('next_obs', _vp), ('next_obs_pitch', C.c_int64), ('action', _vp),
+    ('action_pitch', C.c_int64), ('mean', _vp), ('std', _vp), ('x_cur', _vp), ('x_next', _vp),
+    ('x_pi', _vp), ('x_pitch', C.c_int64), ('stream', _vp))
+SAC_HEAD_SAMPLE_ARGS = (
+    ('n_rows', C.c_int64), ('n_actions', C.c_int64), ('jobs', C.POINTER(BxSacSampleJob)),
+    ('n_jobs', C.c_int32), ('min_std', C.c_float), ('stream', _vp))
+SAC_HEAD_LOSSES_ARGS = (
+    ('n_rows', C.c_int64), ('n_critics', C.c_int32), ('lp_alpha', _vp), ('lp_next', _vp),
+    ('lp_pi', _vp), ('q', C.POINTER(BxSacQ)), ('reward', _vp), ('reward_stride', C.c_int64),
+    ('discount', _vp), ('discount_stride', C.c_int64), ('truncation', _vp),
+    ('truncation_stride', C.c_int64), ('log_alpha', _vp), ('reward_scaling', C.c_float),
+    ('discounting', C.c_float), ('target_entropy', C.c_float), ('g_lp', _vp), ('workspace', _vp),
+    ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
+SAC_HEAD_SAMPLE_BACKWARD_ARGS = (
+    ('n_rows', C.c_int64), ('n_actions', C.c_int64), ('n_critics', C.c_int32), ('logits', _vp),
+    ('logits_pitch', C.c_int64), ('eps', _vp), ('eps_pitch', C.c_int64), ('g_lp', _vp),
+    ('da', C.POINTER(BxSacDaction)), ('min_std', C.c_float), ('dlogits', _vp),
+    ('dlogits_pitch', C.c_int64), ('losses', _vp), ('dlog_alpha', _vp), ('workspace', _vp),
+    ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
 OPT_MAX_TENSORS = 32  # BX_OPT_MAX_TENSORS
 OPT_CHUNK = 1024  # elements of one tensor that one workgroup of bx_adam_step owns
 
@@ -244,6 +291,9 @@ ARGS = {'bx_system_blob': SYSTEM_BLOB_ARGS,
         'bx_replay_insert': REPLAY_INSERT_ARGS, 'bx_replay_sample': REPLAY_SAMPLE_ARGS,
         'bx_mlp_sizes': MLP_SIZES_ARGS, 'bx_mlp_forward': MLP_FORWARD_ARGS,
         'bx_mlp_backward': MLP_BACKWARD_ARGS, 'bx_ppo_head': PPO_HEAD_ARGS,
+        'bx_sac_head_prep': SAC_HEAD_PREP_ARGS, 'bx_sac_head_sample': SAC_HEAD_SAMPLE_ARGS,
+        'bx_sac_head_losses': SAC_HEAD_LOSSES_ARGS,
+        'bx_sac_head_sample_backward': SAC_HEAD_SAMPLE_BACKWARD_ARGS,
         'bx_opt_sizes': OPT_SIZES_ARGS, 'bx_adam_step': ADAM_STEP_ARGS}
 SIGNATURES = {name: ([t for _, t in args], C.c_int) for name, args in ARGS.items()}
 

@@ -1,6 +1,6 @@
 // bx_capi_learn.cpp — the C ABI's learner side (include/brax_amd.h): the RNG
 // slabs, GAE, the evolution agents' perturbation and update, the replay queue,
-// the MLPs, the PPO loss head and the optimiser step, none on a system
+// the MLPs, the PPO and SAC loss heads and the optimiser step, none on a system
 #include <algorithm>
 #include <initializer_list>
 
@@ -10,6 +10,7 @@
 #include "pbd_launch.h"  // (the slab and evolution launchers)
 #include "ppo_head_launch.h"
 #include "replay_launch.h"
+#include "sac_head_launch.h"
 #include "train_launch.h"
 
 using namespace bx;
@@ -130,6 +131,30 @@ int mlp_args(const bx_mlp* net, int64_t rows, int64_t x_stride, MlpNet* m) {
   if (x_stride < net->in[0])
     return fail("x_stride " + std::to_string(x_stride) + " below the input width " +
                 std::to_string(net->in[0]));
+  return 0;
+}
+
+// the SAC heads' shared checks: the row count, then the action count
+int sac_rows(int64_t n_rows) {
+  if (n_rows < 0) return fail("negative n_rows");
+  if (n_rows > ((int64_t)1 << 31)) return fail("too many rows for one launch");
+  return 0;
+}
+int sac_actions(int64_t n_actions) {
+  if (n_actions < 1) return fail("n_actions must be >= 1");
+  if (n_actions > ((int64_t)1 << 20)) return fail("too many actions");
+  return 0;
+}
+int sac_critics(int32_t n_critics) {
+  if (n_critics < 1 || n_critics > BX_SAC_MAX_CRITICS)
+    return fail("n_critics " + std::to_string(n_critics) + " outside 1.." +
+                std::to_string(BX_SAC_MAX_CRITICS));
+  return 0;
+}
+int sac_pitch(const char* name, int64_t pitch, int64_t width) {
+  if (pitch < width)
+    return fail(std::string(name) + " " + std::to_string(pitch) + " below the row width " +
+                std::to_string(width));
   return 0;
 }
 
@@ -367,6 +392,156 @@ int bx_ppo_head(int64_t n_steps, int64_t n_envs, int64_t n_actions, const bx_seq
   a.adv = *advantages;
   ppo_head_carve(a, workspace);
   HIP_OK(launch_ppo_head(a, st));
+  return 0;
+}
+
+int bx_sac_head_prep(int64_t n_rows, int64_t n_obs, int64_t n_actions, const float* obs,
+                     int64_t obs_pitch, const float* next_obs, int64_t next_obs_pitch,
+                     const float* action, int64_t action_pitch, const float* mean,
+                     const float* std, float* x_cur, float* x_next, float* x_pi, int64_t x_pitch,
+                     void* stream) {
+  if (sac_rows(n_rows)) return 1;
+  if (n_obs < 1) return fail("n_obs must be >= 1");
+  if (n_obs > ((int64_t)1 << 20)) return fail("too many observations");
+  if (sac_actions(n_actions)) return 1;
+  if (n_rows == 0) return 0;
+  if (!obs || !next_obs || !action || !x_cur || !x_next || !x_pi) return fail("null argument");
+  if (!mean != !std) return fail("one of mean and std is null");
+  if (sac_pitch("obs_pitch", obs_pitch, n_obs) || sac_pitch("next_obs_pitch", next_obs_pitch, n_obs) ||
+      sac_pitch("action_pitch", action_pitch, n_actions) ||
+      sac_pitch("x_pitch", x_pitch, n_obs + n_actions))
+    return 1;
+  STREAM_SCOPE(stream, st);
+  SacPrepArgs a{};
+  a.B = n_rows;
+  a.O = n_obs;
+  a.A = n_actions;
+  a.obs = obs;
+  a.next_obs = next_obs;
+  a.action = action;
+  a.obs_pitch = obs_pitch;
+  a.next_obs_pitch = next_obs_pitch;
+  a.action_pitch = action_pitch;
+  a.mean = mean;
+  a.std = std;
+  a.x_cur = x_cur;
+  a.x_next = x_next;
+  a.x_pi = x_pi;
+  a.x_pitch = x_pitch;
+  HIP_OK(launch_sac_prep(a, st));
+  return 0;
+}
+
+int bx_sac_head_sample(int64_t n_rows, int64_t n_actions, const bx_sac_sample_job* jobs,
+                       int32_t n_jobs, float min_std, void* stream) {
+  if (sac_rows(n_rows) || sac_actions(n_actions)) return 1;
+  if (n_jobs < 1 || n_jobs > BX_SAC_MAX_JOBS)
+    return fail("n_jobs " + std::to_string(n_jobs) + " outside 1.." + std::to_string(BX_SAC_MAX_JOBS));
+  if (n_rows == 0) return 0;
+  if (!jobs) return fail("null argument");
+  SacSampleArgs a{};
+  for (int k = 0; k < n_jobs; ++k) {
+    const bx_sac_sample_job& j = jobs[k];
+    if (!j.logits || !j.eps || !j.log_prob)
+      return fail("job " + std::to_string(k) + ": null logits, eps or log_prob");
+    if (sac_pitch("logits_pitch", j.logits_pitch, 2 * n_actions) ||
+        sac_pitch("eps_pitch", j.eps_pitch, n_actions) ||
+        (j.action && sac_pitch("action_pitch", j.action_pitch, n_actions)))
+      return 1;
+    a.job[k] = j;
+  }
+  a.B = n_rows;
+  a.A = n_actions;
+  a.n_jobs = n_jobs;
+  a.min_std = min_std;
+  STREAM_SCOPE(stream, st);
+  HIP_OK(launch_sac_sample(a, st));
+  return 0;
+}
+
+int bx_sac_head_losses(int64_t n_rows, int32_t n_critics, const float* lp_alpha,
+                       const float* lp_next, const float* lp_pi, const bx_sac_q* q,
+                       const float* reward, int64_t reward_stride, const float* discount,
+                       int64_t discount_stride, const float* truncation,
+                       int64_t truncation_stride, const float* log_alpha, float reward_scaling,
+                       float discounting, float target_entropy, float* g_lp, void* workspace,
+                       int64_t* workspace_bytes, void* stream) {
+  if (!workspace_bytes) return fail("null argument");
+  if (sac_rows(n_rows) || sac_critics(n_critics)) return 1;
+  const int64_t need = sac_head_workspace_bytes(n_rows);
+  if (size_query(workspace, workspace_bytes, need)) return 0;
+  if (n_rows == 0) return 0;
+  if (!lp_alpha || !lp_next || !lp_pi || !q || !reward || !discount || !truncation || !log_alpha ||
+      !g_lp)
+    return fail("null argument");
+  for (int c = 0; c < n_critics; ++c)
+    if (!q->q_old[c] || !q->next_q[c] || !q->q_pi[c] || !q->dq_old[c] || !q->dq_pi[c])
+      return fail("critic " + std::to_string(c) + ": null pointer");
+  if (check_workspace(workspace, *workspace_bytes, need, 16)) return 1;
+  STREAM_SCOPE(stream, st);
+  SacLossesArgs a{};
+  a.B = n_rows;
+  a.C = n_critics;
+  a.lp_alpha = lp_alpha;
+  a.lp_next = lp_next;
+  a.lp_pi = lp_pi;
+  a.q = *q;
+  a.reward = reward;
+  a.discount = discount;
+  a.truncation = truncation;
+  a.reward_stride = reward_stride;
+  a.discount_stride = discount_stride;
+  a.truncation_stride = truncation_stride;
+  a.log_alpha = log_alpha;
+  a.reward_scaling = reward_scaling;
+  a.discounting = discounting;
+  a.target_entropy = target_entropy;
+  a.g_lp = g_lp;
+  a.part = (double*)workspace;
+  HIP_OK(launch_sac_losses(a, st));
+  return 0;
+}
+
+int bx_sac_head_sample_backward(int64_t n_rows, int64_t n_actions, int32_t n_critics,
+                                const float* logits, int64_t logits_pitch, const float* eps,
+                                int64_t eps_pitch, const float* g_lp, const bx_sac_daction* da,
+                                float min_std, float* dlogits, int64_t dlogits_pitch,
+                                float* losses, float* dlog_alpha, void* workspace,
+                                int64_t* workspace_bytes, void* stream) {
+  if (!workspace_bytes) return fail("null argument");
+  if (sac_rows(n_rows) || sac_actions(n_actions) || sac_critics(n_critics)) return 1;
+  const int64_t need = sac_head_workspace_bytes(n_rows);
+  if (size_query(workspace, workspace_bytes, need)) return 0;
+  if (n_rows == 0) return 0;
+  if (!logits || !eps || !g_lp || !da || !dlogits || !losses || !dlog_alpha)
+    return fail("null argument");
+  if (sac_pitch("logits_pitch", logits_pitch, 2 * n_actions) ||
+      sac_pitch("eps_pitch", eps_pitch, n_actions) ||
+      sac_pitch("dlogits_pitch", dlogits_pitch, 2 * n_actions))
+    return 1;
+  for (int c = 0; c < n_critics; ++c) {
+    if (!da->ptr[c]) return fail("critic " + std::to_string(c) + ": null pointer");
+    if (sac_pitch("daction pitch", da->pitch[c], n_actions)) return 1;
+  }
+  if (check_workspace(workspace, *workspace_bytes, need, 16)) return 1;
+  STREAM_SCOPE(stream, st);
+  SacBackwardArgs a{};
+  a.B = n_rows;
+  a.A = n_actions;
+  a.C = n_critics;
+  a.min_std = min_std;
+  a.logits = logits;
+  a.eps = eps;
+  a.g_lp = g_lp;
+  a.logits_pitch = logits_pitch;
+  a.eps_pitch = eps_pitch;
+  a.da = *da;
+  a.dlogits = dlogits;
+  a.dlogits_pitch = dlogits_pitch;
+  a.part = (const double*)workspace;
+  a.losses = losses;
+  a.dlog_alpha = dlog_alpha;
+  HIP_OK(launch_sac_sample_backward(a, st));
   return 0;
 }
 

@@ -32,7 +32,7 @@ import torch
 from brax_amd.envs import wrappers
 from brax_amd.envs.evaluator import Evaluator
 from brax_amd.envs.policy import MLPPolicy, policy_rollout
-from brax_amd.training import optim, sac_losses, sac_networks
+from brax_amd.training import optim, sac_head, sac_losses, sac_networks
 from brax_amd.training.networks import Layers, parameters
 from brax_amd.training.ppo import RunningStatistics
 from brax_amd.training.replay_buffers import UniformSamplingQueue, transition_fields
@@ -128,9 +128,42 @@ def _apply(optimizer, params, grads):
   optimizer.zero_grad(set_to_none=True)
 
 
+def _chained_gradients(ts: TrainingState, normalizer, transitions, eps, reward_scaling, discounting,
+                       fused_mlp):
+  """The three losses as torch expressions (`sac_losses`) and autograd's
+  gradients of them: `(a_grads, c_grads, p_grads, metrics)`."""
+  eps_alpha, eps_critic, eps_actor = eps
+  policy_params = parameters(ts.policy_layers)
+  q_params = sac_networks.q_parameters(ts.q_layers)
+  a_loss = sac_losses.alpha_loss(ts.log_alpha, ts.policy_layers, normalizer, transitions, eps_alpha,
+                                 fused_mlp)
+  alpha = torch.exp(ts.log_alpha.detach())
+  c_loss = sac_losses.critic_loss(ts.q_layers, ts.policy_layers, normalizer, ts.target_q_layers,
+                                  alpha, transitions, eps_critic, reward_scaling, discounting,
+                                  fused_mlp)
+  p_loss = sac_losses.actor_loss(ts.policy_layers, normalizer, ts.q_layers, alpha, transitions,
+                                 eps_actor, fused_mlp)
+  a_grads = torch.autograd.grad(a_loss, [ts.log_alpha])
+  c_grads = torch.autograd.grad(c_loss, q_params)
+  p_grads = torch.autograd.grad(p_loss, policy_params)
+  return a_grads, c_grads, p_grads, {'critic_loss': c_loss.detach(), 'actor_loss': p_loss.detach(),
+                                     'alpha_loss': a_loss.detach()}
+
+
+def _gradients(ts, normalizer, transitions, eps, reward_scaling, discounting, fused_mlp, fused_head):
+  if fused_head is not False:
+    why = sac_head.fused_supported(ts, normalizer, transitions, eps)
+    if why is None:
+      return sac_head.gradients(ts, normalizer, transitions, eps, reward_scaling, discounting,
+                                fused_mlp)
+    if fused_head is True:
+      raise NotImplementedError(f'no fused sac head: {why}')
+  return _chained_gradients(ts, normalizer, transitions, eps, reward_scaling, discounting, fused_mlp)
+
+
 def sgd_step(ts: TrainingState, normalizer, transitions: Mapping[str, torch.Tensor],
              eps: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], reward_scaling: float = 1.0,
-             discounting: float = 0.9, tau: float = 0.005, fused_mlp=False):
+             discounting: float = 0.9, tau: float = 0.005, fused_mlp=False, fused_head=False):
   """One gradient step in the reference's order (`train.py:214-269`).
 
   The alpha update comes first, but the critic and actor losses read `exp` of
@@ -149,25 +182,19 @@ def sgd_step(ts: TrainingState, normalizer, transitions: Mapping[str, torch.Tens
     eps: the standard-normal draws `(B, A)` of the alpha, critic and actor
       losses' samples (the reference's three keys).
     fused_mlp: the losses' `fused_mlp` (`networks.mlp`'s `fused`).
+    fused_head: how the three gradients are taken (False: `sac_losses` and
+      autograd; True: `sac_head.gradients`, four launches between the networks,
+      or NotImplementedError; None: that where it applies).
   Returns:
-    the metrics (detached tensors): critic_loss, actor_loss, alpha_loss, alpha.
+    the metrics (detached tensors): critic_loss, actor_loss, alpha_loss, alpha;
+    from the kernels a `sac_head.Metrics`, whose `vector` is the three losses.
   """
   if ts.fused_optimizer is not None and tau != ts.fused_optimizer.groups[1]['tau']:
     raise ValueError(f"tau {tau} is not the fused optimiser's {ts.fused_optimizer.groups[1]['tau']}")
-  eps_alpha, eps_critic, eps_actor = eps
   policy_params = parameters(ts.policy_layers)
   q_params = sac_networks.q_parameters(ts.q_layers)
-  a_loss = sac_losses.alpha_loss(ts.log_alpha, ts.policy_layers, normalizer, transitions, eps_alpha,
-                                 fused_mlp)
-  alpha = torch.exp(ts.log_alpha.detach())
-  c_loss = sac_losses.critic_loss(ts.q_layers, ts.policy_layers, normalizer, ts.target_q_layers,
-                                  alpha, transitions, eps_critic, reward_scaling, discounting,
-                                  fused_mlp)
-  p_loss = sac_losses.actor_loss(ts.policy_layers, normalizer, ts.q_layers, alpha, transitions,
-                                 eps_actor, fused_mlp)
-  a_grads = torch.autograd.grad(a_loss, [ts.log_alpha])
-  c_grads = torch.autograd.grad(c_loss, q_params)
-  p_grads = torch.autograd.grad(p_loss, policy_params)
+  a_grads, c_grads, p_grads, metrics = _gradients(ts, normalizer, transitions, eps, reward_scaling,
+                                                  discounting, fused_mlp, fused_head)
   if ts.fused_optimizer is not None:
     ts.fused_optimizer.step(grads=[*a_grads, *c_grads, *p_grads])
   else:
@@ -180,8 +207,8 @@ def sgd_step(ts: TrainingState, normalizer, transitions: Mapping[str, torch.Tens
           for t, q in zip(t_wb, q_wb):
             t.copy_(t * (1 - tau) + q * tau)
   ts.gradient_steps += 1
-  return {'critic_loss': c_loss.detach(), 'actor_loss': p_loss.detach(),
-          'alpha_loss': a_loss.detach(), 'alpha': torch.exp(ts.log_alpha.detach())}
+  metrics['alpha'] = torch.exp(ts.log_alpha.detach())
+  return metrics
 
 
 def _detached(layers):
@@ -197,7 +224,7 @@ class Learner:
                tau: float = 0.005, normalize_observations: bool = False, seed: int = 0,
                network_factory=sac_networks.make_sac_networks, device=None,
                action_repeat: int = 1, fused_buffer: Optional[bool] = None, fused_mlp=False,
-               fused_adam=False):
+               fused_adam=False, fused_head=False):
     self.env, self.device = env, torch.device(device)
     self.num_envs, self.action_repeat = int(num_envs), int(action_repeat)
     self.batch_size, self.grad_updates_per_step = int(batch_size), int(grad_updates_per_step)
@@ -205,7 +232,7 @@ class Learner:
     self.seed, self.fused_buffer, self.fused_mlp = int(seed), fused_buffer, fused_mlp
     self.loss_kwargs = dict(reward_scaling=reward_scaling, discounting=discounting, tau=tau)
     O, A = env.observation_size, env.action_size
-    self.fused_adam = fused_adam
+    self.fused_adam, self.fused_head = fused_adam, fused_head
     self.ts = init_training_state(O, A, learning_rate, network_factory, seed, self.device,
                                   fused_adam=fused_adam, tau=tau)
     self.normalizer = RunningStatistics(O, self.device) if normalize_observations else None
@@ -274,10 +301,16 @@ class Learner:
       mb = {k: v[g * self.batch_size:(g + 1) * self.batch_size] for k, v in transitions.items()}
       eps = tuple(torch.randn((self.batch_size, A), generator=self._gen, device=self.device)
                   for _ in range(3))
-      for k, v in sgd_step(self.ts, self._mean_std, mb, eps, fused_mlp=self.fused_mlp,
-                           **self.loss_kwargs).items():
+      metrics = sgd_step(self.ts, self._mean_std, mb, eps, fused_mlp=self.fused_mlp,
+                         fused_head=self.fused_head, **self.loss_kwargs)
+      vector = getattr(metrics, 'vector', None)
+      if vector is not None:  # the three losses in one addition
+        metrics = {'losses': vector, 'alpha': metrics['alpha']}
+      for k, v in metrics.items():
         sums[k] = v + sums.get(k, 0)
     self.actor.load_(_detached(self.ts.policy_layers))
+    if 'losses' in sums:
+      sums = {**dict(zip(sac_head.METRICS, sums['losses'])), 'alpha': sums['alpha']}
     return {k: v / self.grad_updates_per_step for k, v in sums.items()}
 
   def training_step(self):
@@ -298,7 +331,8 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
           deterministic_eval: bool = False, network_factory=sac_networks.make_sac_networks,
           progress_fn: Callable[[int, dict], None] = lambda *args: None,
           checkpoint_logdir: Optional[str] = None, eval_env=None, device=None,
-          fused_buffer: Optional[bool] = None, fused_mlp=False, fused_adam=False):
+          fused_buffer: Optional[bool] = None, fused_mlp=False, fused_adam=False,
+          fused_head=False):
   """SAC training; the reference's arguments and defaults
   (`sac/train.py:106-129`).
 
@@ -323,6 +357,9 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
       (False: three `torch.optim.Adam` and a loop over the target tensors; True:
       one `optim.FusedAdam` step, one launch, or NotImplementedError; None: that
       where it applies).
+    fused_head: the three losses and their gradients between the networks
+      (False: `sac_losses` and autograd; True: `sac_head.gradients`, four
+      launches, or NotImplementedError; None: that where it applies).
   Returns:
     `(make_policy, params, metrics)`: `make_policy(params, deterministic=False)`
     gives an `MLPPolicy`; `params` is (the normaliser or None, the policy
@@ -355,7 +392,8 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
                     reward_scaling=reward_scaling, tau=tau,
                     normalize_observations=normalize_observations, seed=seed,
                     network_factory=network_factory, device=dev, action_repeat=action_repeat,
-                    fused_buffer=fused_buffer, fused_mlp=fused_mlp, fused_adam=fused_adam)
+                    fused_buffer=fused_buffer, fused_mlp=fused_mlp, fused_adam=fused_adam,
+                    fused_head=fused_head)
   key = np.array([0, int(seed)], np.uint32)  # jax.random.PRNGKey(seed) layout
   key_env, key_eval = wrappers.split_key(key)
   learner.reset(key_env)

@@ -1004,6 +1004,116 @@ int bx_adam_step(const bx_opt_tensor* t, int32_t n_tensors, int64_t step, double
                  double beta2, float eps, void* stream);
 
 /*
+ * The SAC loss heads: what a SAC gradient step computes between its network
+ * evaluations (brax_amd/training/sac_losses.py), in FOUR launches on `stream`,
+ * one per entry point, called in this order around the networks. B rows, O
+ * observations, A actions, C critics; everything float32; a `pitch` is a
+ * row's stride in elements (the row itself has unit stride).
+ *
+ * bx_sac_head_prep writes the critics' three inputs (B, O + A) at one pitch:
+ *   x_cur  = [n(obs) | action]     x_next = [n(next_obs) | .]
+ *   x_pi   = [n(obs) | .]          n(o) = (o - mean) / std, two float32
+ *                                  operations; mean = std = NULL: n(o) = o
+ * The action columns of x_next and x_pi are not written (bx_sac_head_sample
+ * fills them). mean and std are (O,).
+ *
+ * bx_sac_head_sample runs n_jobs (1..BX_SAC_MAX_JOBS) samples in one launch.
+ * Per job, logits (B, 2 A) = [loc | s], eps (B, A):
+ *   scale      = softplus(s) + min_std     (softplus(x) = x above 20, else
+ *                                           log1p(exp(x)))
+ *   raw        = loc + scale eps
+ *   action     = tanh(raw)                 (B, A); NULL: not wanted
+ *   log_prob   = sum_a -0.5 z^2 - 0.5 log 2 pi - log scale - det(raw),
+ *                z = (raw - loc) / scale, det(x) = 2 (log 2 - x - softplus(-2 x))
+ *
+ * bx_sac_head_losses reads the three jobs' log-probs (B,) and the critics'
+ * outputs, C separate contiguous (B,) arrays each (bx_sac_q): q_old =
+ * Q(x_cur), next_q = Qtarget(x_next), q_pi = Q(x_pi); reward, discount and
+ * truncation (B,) with an element stride; log_alpha on the device. With alpha
+ * = exp(*log_alpha):
+ *   y_b        = reward_b reward_scaling + discount_b discounting
+ *                (min_c next_q_cb - alpha lp_next_b)
+ *   e_bc       = (q_old_cb - y_b) (1 - truncation_b)
+ *   dq_old_cb  = e_bc (1 - truncation_b) / (B C)
+ *   dq_pi_cb   = -1/B at the minimal q_pi_cb (the lowest c of a tie), else 0
+ *   g_lp_b     = alpha / B
+ * and leaves each workgroup's sums of e^2, of alpha lp_pi - min_c q_pi and of
+ * alpha (-lp_alpha - target_entropy) in the workspace as doubles.
+ *
+ * bx_sac_head_sample_backward is the actor sample's backward pass, with g =
+ * g_lp and da = the sum over c, in the order of c, of the C arrays da->ptr[c]
+ * (B, A) (the action columns of each critic's input gradient):
+ *   u = g 2 tanh(raw) + da (1 - tanh(raw)^2)
+ *   dlogits = [u | (u eps - g / scale) sigmoid(s)]            (B, 2 A)
+ * One more workgroup sums the workspace's partials (the SAME workspace the
+ * losses call of this step wrote) into
+ *   losses[0] = 0.5/(B C) sum e^2                              (critic)
+ *   losses[1] = 1/B sum (alpha lp_pi - min_c q_pi)             (actor)
+ *   losses[2] = 1/B sum alpha (-lp_alpha - target_entropy)     (alpha)
+ * and *dlog_alpha = losses[2], the alpha loss's derivative in log_alpha.
+ *
+ * No floating-point atomics: every sum across rows is float64, added over the
+ * lanes and waves of a workgroup in a fixed tree and over the workgroups'
+ * partials lane-strided in ascending order, so the bits depend on (B, A, C)
+ * and the inputs alone. alpha is never read on the host, so a step can be
+ * captured. NaN and Inf propagate as IEEE has them; a non-finite input of row
+ * b reaches no other row's outputs (and the losses it is summed into).
+ *
+ * The workspace is the caller's (device memory, 16-byte aligned) of
+ * *workspace_bytes bytes; with workspace == NULL the call launches nothing
+ * and writes the size it needs to *workspace_bytes: 24 ceil(B / 256), rounded
+ * up to 16. Outputs must not overlap the inputs, the workspace or each other.
+ * A null workspace_bytes, n_rows < 0 or above 2^31, n_obs < 1, n_actions < 1
+ * or above 2^20, n_jobs outside 1..BX_SAC_MAX_JOBS, n_critics outside
+ * 1..BX_SAC_MAX_CRITICS, a null required pointer, one of mean and std alone, a
+ * pitch below its row's width, a workspace that is too small or misaligned
+ * fail before any device call; n_rows = 0 launches nothing. No system handle:
+ * the launches go to the device that owns `stream` (the current device for
+ * NULL). (Additive: no ABI bump.) */
+#define BX_SAC_MAX_CRITICS 4
+#define BX_SAC_MAX_JOBS 3
+typedef struct bx_sac_sample_job {
+  const float* logits;
+  int64_t logits_pitch;
+  const float* eps;
+  int64_t eps_pitch;
+  float* action; /* NULL: not wanted */
+  int64_t action_pitch;
+  float* log_prob;
+} bx_sac_sample_job;
+typedef struct bx_sac_q {
+  const float* q_old[BX_SAC_MAX_CRITICS];
+  const float* next_q[BX_SAC_MAX_CRITICS];
+  const float* q_pi[BX_SAC_MAX_CRITICS];
+  float* dq_old[BX_SAC_MAX_CRITICS];
+  float* dq_pi[BX_SAC_MAX_CRITICS];
+} bx_sac_q;
+typedef struct bx_sac_daction {
+  const float* ptr[BX_SAC_MAX_CRITICS];
+  int64_t pitch[BX_SAC_MAX_CRITICS];
+} bx_sac_daction;
+int bx_sac_head_prep(int64_t n_rows, int64_t n_obs, int64_t n_actions, const float* obs,
+                     int64_t obs_pitch, const float* next_obs, int64_t next_obs_pitch,
+                     const float* action, int64_t action_pitch, const float* mean,
+                     const float* std, float* x_cur, float* x_next, float* x_pi, int64_t x_pitch,
+                     void* stream);
+int bx_sac_head_sample(int64_t n_rows, int64_t n_actions, const bx_sac_sample_job* jobs,
+                       int32_t n_jobs, float min_std, void* stream);
+int bx_sac_head_losses(int64_t n_rows, int32_t n_critics, const float* lp_alpha,
+                       const float* lp_next, const float* lp_pi, const bx_sac_q* q,
+                       const float* reward, int64_t reward_stride, const float* discount,
+                       int64_t discount_stride, const float* truncation,
+                       int64_t truncation_stride, const float* log_alpha, float reward_scaling,
+                       float discounting, float target_entropy, float* g_lp, void* workspace,
+                       int64_t* workspace_bytes, void* stream);
+int bx_sac_head_sample_backward(int64_t n_rows, int64_t n_actions, int32_t n_critics,
+                                const float* logits, int64_t logits_pitch, const float* eps,
+                                int64_t eps_pitch, const float* g_lp, const bx_sac_daction* da,
+                                float min_std, float* dlogits, int64_t dlogits_pitch,
+                                float* losses, float* dlog_alpha, void* workspace,
+                                int64_t* workspace_bytes, void* stream);
+
+/*
  * Standalone HBM-streaming phase kernels over a structure-of-arrays batch
  * (the integrator and collider phases benchmarked in isolation).
  * SoA: field plane k, body b, env e at base[k*plane + b*n_envs + e]; the 13
