@@ -26,6 +26,7 @@ from brax_amd.envs import packed, wrappers
 from brax_amd.envs.env import State
 from brax_amd.envs.policy import MLPPolicy, fused_supported, step_noise
 from brax_amd.envs.rollout import chain_options
+from brax_amd.fused import use_kernel
 from brax_amd.system import _stream
 
 
@@ -131,10 +132,7 @@ def eval_rollout(env, state: State, k: Optional[int] = None, policy: Optional[ML
   em_in = state.info.get('eval_metrics')
   if not isinstance(em_in, wrappers.EvalMetrics):
     raise ValueError(f'Incorrect type for state_metrics: {type(em_in)}')
-  why = None if fused is False else eval_supported(env, policy)
-  if fused is True and why is not None:
-    raise NotImplementedError(f'no fused evaluation: {why}')
-  if fused is False or why is not None:
+  if not use_kernel(fused, 'evaluation', lambda: eval_supported(env, policy)):
     return _chained(env, state, policy, actions, K, seed, offset, step_stride)
   u, opts = chain_options(inner)
   dev = u.sys.device

@@ -27,6 +27,7 @@ from brax_amd.base import pack_qp
 from brax_amd.envs import packed
 from brax_amd.envs.env import State, _f32
 from brax_amd.envs.rollout import Trajectory, chain_options, trajectory
+from brax_amd.fused import use_kernel
 from brax_amd.system import _stream
 
 _ACTIVATIONS = {
@@ -333,10 +334,7 @@ def policy_rollout(env, state: State, policy: MLPPolicy, k: int, seed: int = 0, 
   """
   if k < 1:
     raise ValueError(f'k must be >= 1, got {k}')
-  why = None if fused is False else fused_supported(env, policy)
-  if fused is True and why is not None:
-    raise NotImplementedError(f'no fused policy rollout: {why}')
-  if fused is False or why is not None:
+  if not use_kernel(fused, 'policy rollout', lambda: fused_supported(env, policy)):
     return _chained(env, state, policy, int(k), seed, offset, step_stride)
   u, opts = chain_options(env)
   dev = u.sys.device

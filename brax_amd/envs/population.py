@@ -36,6 +36,7 @@ from brax_amd.envs.env import State, _f32
 from brax_amd.envs.policy import (_ACTIVATIONS, MLPPolicy, fused_supported, normal_slabs,
                                   normal_tanh_head, step_noise)
 from brax_amd.envs.rollout import chain_options
+from brax_amd.fused import use_kernel
 from brax_amd.system import _stream
 
 
@@ -305,10 +306,7 @@ def population_rollout(env, state: State, population, k: Optional[int] = None, s
   B = state.obs.shape[0]
   if pop is not None and pop.n_members != B:
     raise ValueError(f'the population holds {pop.n_members} members, the state {B} envs')
-  why = None if fused is False else population_supported(env, population)
-  if fused is True and why is not None:
-    raise NotImplementedError(f'no fused population rollout: {why}')
-  if fused is False or why is not None:
+  if not use_kernel(fused, 'population rollout', lambda: population_supported(env, population)):
     return _chained(inner, state, policy, pop, K, seed, offset, reward_shift, moments, carry)
   u, opts = chain_options(inner)
   dev = u.sys.device

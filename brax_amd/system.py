@@ -36,6 +36,13 @@ def _stream(device_index=None):
   return C.c_void_p(torch.cuda.current_stream(device_index).cuda_stream)
 
 
+def launch(dev, entry: str, *args):
+  """The learner entry points' call: with `dev` current, the library's `entry`
+  on `args` and then the caller's stream on `dev`, its result checked."""
+  with torch.cuda.device(dev):
+    _native.check(getattr(_native.lib(), entry)(*args, _stream(dev.index)))
+
+
 def _field(t, batched):
   if t.dtype != torch.float32 or not t.is_cuda:
     raise TypeError('QP fields must be float32 device tensors')

@@ -17,4 +17,5 @@ from brax_amd.training.replay_buffers import UniformSamplingQueue, transition_fi
 from brax_amd.training.sac_networks import make_sac_networks
 # (the module, not its function of the same name: `training.fused_mlp.fused_mlp`)
 from brax_amd.training import fused_mlp
-from brax_amd.training.ppo import Learner, RunningStatistics, step_accounting, train, transitions
+from brax_amd.training.ppo import Learner, step_accounting, train, transitions
+from brax_amd.training.running_statistics import RunningStatistics

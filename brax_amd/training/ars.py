@@ -17,12 +17,9 @@ own evaluation schedule (no initial evaluation).
 import dataclasses
 from typing import Callable, Optional, Tuple
 
-import numpy as np
 import torch
 
-from brax_amd.envs import wrappers
-from brax_amd.envs.evaluator import Evaluator
-from brax_amd.training import es
+from brax_amd.training import driver, es
 
 
 def ars_weights(scores: torch.Tensor, top_directions: int
@@ -136,15 +133,13 @@ def train(environment, num_timesteps: int = 100, episode_length: int = 1000,
   num_envs = number_of_directions * 2  # noise + anti noise
   sched = eval_schedule(num_timesteps, num_evals)
   dev = torch.device('cuda' if device is None else device)
-  env, eval_env = es._make_envs(environment, eval_env, num_envs, num_eval_envs, episode_length,  # pylint: disable=protected-access
-                                action_repeat, dev)
+  env, eval_env = driver.make_envs(environment, eval_env, num_envs, num_eval_envs, episode_length,
+                                   action_repeat, dev)
   learner = Learner(env, number_of_directions, top_directions, step_size, episode_length,
                     action_repeat, exploration_noise_std, seed, normalize_observations,
                     reward_shift, network_factory, dev, fused)
-  key_eval = wrappers.split_key(np.array([0, int(seed)], np.uint32))[1]
-  evaluator = Evaluator(eval_env, learner.policy, num_eval_envs=num_eval_envs,
-                        episode_length=episode_length, action_repeat=action_repeat,
-                        seed=int(wrappers.key_to_seed(key_eval)) & 0x7FFFFFFF, device=dev)
-  metrics = es.run(learner, learner.policy, evaluator, num_timesteps, sched.first_eval_step,
-                   sched.num_env_steps_between_evals, False, progress_fn)
+  evaluator = driver.make_evaluator(eval_env, learner.policy, seed, num_eval_envs, episode_length,
+                                    action_repeat, dev)
+  metrics = driver.run(learner, learner.policy, evaluator, num_timesteps, sched.first_eval_step,
+                       sched.num_env_steps_between_evals, False, progress_fn)
   return learner.make_policy, learner.params, metrics

@@ -25,6 +25,8 @@ from typing import Optional
 import torch
 
 from brax_amd import _native, abi
+from brax_amd.fused import use_kernel
+from brax_amd.system import launch
 from brax_amd.training import networks
 
 
@@ -89,7 +91,6 @@ class _FusedMlp(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, x2, activation, want, *params):
-    from brax_amd.system import _stream  # pylint: disable=import-outside-toplevel
     dev = x2.device
     params = tuple(p.detach() for p in params)
     rows = x2.shape[0]
@@ -98,10 +99,8 @@ class _FusedMlp(torch.autograd.Function):
     saved = torch.empty((rows, hidden), dtype=torch.float32, device=dev) if want else None
     if rows:
       net = _net(params, activation)
-      with torch.cuda.device(dev):
-        _native.check(_native.lib().bx_mlp_forward(
-            C.byref(net), rows, x2.data_ptr(), x2.stride(0), y.data_ptr(),
-            saved.data_ptr() if want and hidden else None, _stream(dev.index)))
+      launch(dev, 'bx_mlp_forward', C.byref(net), rows, x2.data_ptr(), x2.stride(0), y.data_ptr(),
+             saved.data_ptr() if want and hidden else None)
     ctx.activation = activation
     if want:
       ctx.save_for_backward(x2, saved, *params)
@@ -110,7 +109,6 @@ class _FusedMlp(torch.autograd.Function):
   @staticmethod
   @torch.autograd.function.once_differentiable
   def backward(ctx, dy):
-    from brax_amd.system import _stream  # pylint: disable=import-outside-toplevel
     x2, saved, *params = ctx.saved_tensors
     dev = x2.device
     rows = x2.shape[0]
@@ -125,16 +123,13 @@ class _FusedMlp(torch.autograd.Function):
     for l in range(net.n_layers):
       g.dw[l] = None if grads[2 * l] is None else grads[2 * l].data_ptr()
       g.db[l] = None if grads[2 * l + 1] is None else grads[2 * l + 1].data_ptr()
-    lib = _native.lib()
     nbytes = C.c_int64(0)
-    _native.check(lib.bx_mlp_backward(C.byref(net), rows, None, x2.stride(0), None, None, None,
-                                      None, None, C.byref(nbytes), None))
+    _native.check(_native.lib().bx_mlp_backward(C.byref(net), rows, None, x2.stride(0), None, None,
+                                                None, None, None, C.byref(nbytes), None))
     work = torch.empty(((nbytes.value + 3) // 4,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-      _native.check(lib.bx_mlp_backward(
-          C.byref(net), rows, x2.data_ptr(), x2.stride(0), saved.data_ptr() or None,
-          dy.data_ptr(), None if dx is None else dx.data_ptr(), C.byref(g), work.data_ptr(),
-          C.byref(nbytes), _stream(dev.index)))
+    launch(dev, 'bx_mlp_backward', C.byref(net), rows, x2.data_ptr(), x2.stride(0),
+           saved.data_ptr() or None, dy.data_ptr(), None if dx is None else dx.data_ptr(),
+           C.byref(g), work.data_ptr(), C.byref(nbytes))
     return (dx, None, None, *grads)
 
 
@@ -149,12 +144,7 @@ def fused_mlp(layers, x: torch.Tensor, activation: str = 'swish',
       else `networks.mlp`; True raises NotImplementedError where they do not
       apply; False is `networks.mlp`.
   """
-  if fused is False:
-    return networks.mlp(layers, x, activation)
-  why = fused_supported(layers, x, activation)
-  if why is not None:
-    if fused is True:
-      raise NotImplementedError(f'no fused mlp: {why}')
+  if not use_kernel(fused, 'mlp', lambda: fused_supported(layers, x, activation)):
     return networks.mlp(layers, x, activation)
   params = [t for wb in layers for t in wb]
   want = torch.is_grad_enabled() and any(t.requires_grad for t in [x] + params)

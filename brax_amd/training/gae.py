@@ -31,7 +31,9 @@ from typing import Optional, Tuple
 
 import torch
 
-from brax_amd import _native, abi
+from brax_amd import abi
+from brax_amd.fused import use_kernel
+from brax_amd.system import launch
 
 
 def _seq(t):
@@ -108,10 +110,7 @@ def compute_gae(truncation, termination, rewards, values, bootstrap_value, lambd
         raise ValueError(f'out must be two ({T}, {B}) {values.dtype} tensors on {values.device}')
   seqs = tuple(t.detach() for t in seqs)
   boot = bootstrap_value.detach()
-  why = None if fused is False else fused_supported(*seqs, boot)
-  if fused is True and why is not None:
-    raise NotImplementedError(f'no fused compute_gae: {why}')
-  if fused is False or why is not None:
+  if not use_kernel(fused, 'compute_gae', lambda: fused_supported(*seqs, boot)):
     with torch.no_grad():
       vs, adv = _chained(*seqs, boot, lambda_, discount, reward_scaling)
       # (elementwise results take their inputs' layout; the kernel's fresh
@@ -121,7 +120,6 @@ def compute_gae(truncation, termination, rewards, values, bootstrap_value, lambd
       if out is not None:
         vs, adv = out[0].copy_(vs), out[1].copy_(adv)
     return vs, adv
-  from brax_amd.system import _stream  # pylint: disable=import-outside-toplevel
   dev = values.device
   if out is None:
     out = (torch.empty((T, B), dtype=torch.float32, device=dev),
@@ -132,9 +130,7 @@ def compute_gae(truncation, termination, rewards, values, bootstrap_value, lambd
   boot = boot.contiguous()
   tr, term, rew, val = seqs
   args = [_seq(t) for t in (rew, term, tr, val, vs, adv)]
-  with torch.cuda.device(dev):
-    _native.check(_native.lib().bx_compute_gae(
-        T, B, C.byref(args[0]), C.byref(args[1]), C.byref(args[2]), C.byref(args[3]),
-        boot.data_ptr(), C.byref(args[4]), C.byref(args[5]), reward_scaling, discount, lambda_,
-        _stream(dev.index)))
+  launch(dev, 'bx_compute_gae', T, B, C.byref(args[0]), C.byref(args[1]), C.byref(args[2]),
+         C.byref(args[3]), boot.data_ptr(), C.byref(args[4]), C.byref(args[5]), reward_scaling,
+         discount, lambda_)
   return vs, adv

@@ -62,3 +62,8 @@ def mlp(layers: Layers, x: torch.Tensor, activation: str = 'swish', fused=False)
 
 def parameters(*networks: Layers) -> List[torch.Tensor]:
   return [t for layers in networks for wb in layers for t in wb]
+
+
+def detached(layers: Layers) -> Layers:
+  """The layers' tensors without their autograd history (views, no copies)."""
+  return [(w.detach(), b.detach()) for w, b in layers]

@@ -14,13 +14,14 @@ decay, no amsgrad) with the bias corrections taken on the host in double;
                      dict(params=policy_params, lr=3e-4)])
     opt.step(grads)          # or loss.backward(); opt.step()
 """
-import ctypes as C
 import math
 from typing import List, Optional, Sequence
 
 import torch
 
 from brax_amd import _native, abi
+from brax_amd.fused import use_kernel
+from brax_amd.system import launch
 
 _ALIGN = 4  # float32 elements: every arena slice starts on a 16-byte boundary
 
@@ -206,7 +207,6 @@ class FusedAdam:
     `torch.optim.Adam` leaves it."""
     if self.device.type != 'cuda':
       raise _native.NativeError('FusedAdam.step needs CUDA tensors: brax_amd has no CPU fallback')
-    from brax_amd.system import _stream  # pylint: disable=import-outside-toplevel
     if grads is None:
       grads = [p.grad for p in self.params]
     elif len(grads) != len(self.params):
@@ -221,26 +221,24 @@ class FusedAdam:
                          f'{tuple(p.shape)} float32 on {p.device}')
       held.append(g if g.is_contiguous() else g.contiguous())
     self.step_count += 1
-    lib = _native.lib()
-    index = self.device.index
-    elsewhere = index is not None and torch.cuda.current_device() != index
-    if elsewhere:
-      prev = torch.cuda.current_device()
-      torch.cuda.set_device(index)
-    try:
-      stream = _stream(index)
-      for lo, hi, table in self._tables:
-        for k in range(lo, hi):
-          e, g = table[k - lo], held[k]
-          if g is None:
-            e.g, e.n = None, 0
-          else:
-            e.g, e.n = g.data_ptr(), self._slices[k][1]
-        _native.check(lib.bx_adam_step(table, hi - lo, self.step_count, self.betas[0],
-                                       self.betas[1], self.eps, stream))
-    finally:
-      if elsewhere:
-        torch.cuda.set_device(prev)
+    for lo, hi, table in self._tables:
+      for k in range(lo, hi):
+        e, g = table[k - lo], held[k]
+        if g is None:
+          e.g, e.n = None, 0
+        else:
+          e.g, e.n = g.data_ptr(), self._slices[k][1]
+      launch(self.device, 'bx_adam_step', table, hi - lo, self.step_count, self.betas[0],
+             self.betas[1], self.eps)
     # the writes went around torch
     torch.autograd.graph.increment_version(self._written)
     del held
+
+
+def make_adam(groups, fused_adam) -> Optional[FusedAdam]:
+  """`FusedAdam(groups)` with optax.adam's defaults (eps 1e-8, as torch's)
+  where `fused_adam` takes it (the usual rule, see `brax_amd.fused`), else
+  None: the caller builds torch's optimisers."""
+  if use_kernel(fused_adam, 'Adam', lambda: supported(groups)):
+    return FusedAdam(groups, eps=1e-8)
+  return None

@@ -16,20 +16,19 @@ place (`load_`: the buffer the rollout kernel reads keeps its address).
 around it with `Evaluator` as the reference's `acting.Evaluator`.
 """
 import dataclasses
-import time
 from typing import Callable, Optional
 
 import numpy as np
 import torch
 
 from brax_amd.envs import wrappers
-from brax_amd.envs.evaluator import Evaluator
-from brax_amd.envs.policy import MLPPolicy, policy_rollout
-from brax_amd.envs.population import update_running_statistics
+from brax_amd.envs.policy import policy_rollout
+from brax_amd.training import driver
 from brax_amd.training import networks as ppo_networks
 from brax_amd.training import optim
 from brax_amd.training.losses import Transition, ppo_loss
 from brax_amd.training.ppo_head import METRICS
+from brax_amd.training.running_statistics import RunningStatistics
 
 
 @dataclasses.dataclass(frozen=True)
@@ -53,44 +52,6 @@ def step_accounting(num_timesteps: int, num_evals: int, batch_size: int, unroll_
                         num_training_steps_per_epoch, batch_size * num_minibatches // num_envs)
 
 
-class RunningStatistics:
-  """`running_statistics.RunningStatisticsState` for one observation vector:
-  float64 on the host (`update_running_statistics`), with float32 device
-  copies `mean_t` / `std_t` that are updated in place."""
-
-  def __init__(self, size: int, device=None):
-    self.mean = np.zeros(size)
-    self.summed_variance = np.zeros(size)
-    self.count = 0.0
-    self.std = np.ones(size)
-    self.mean_t = torch.zeros((size,), dtype=torch.float32, device=device)
-    self.std_t = torch.ones((size,), dtype=torch.float32, device=device)
-
-  def update(self, obs: torch.Tensor):
-    """`running_statistics.update(state, obs)`, every row of `obs` (..., O)
-    with weight 1: the sums centred on the old mean are taken on `obs`'s
-    device in float64, the O-sized remainder on the host."""
-    rows = obs.reshape(-1, obs.shape[-1])
-    d = rows.double() - torch.as_tensor(self.mean, device=rows.device)
-    self.mean, self.summed_variance, self.count, self.std = update_running_statistics(
-        self.mean, self.summed_variance, self.count,
-        (d.sum(0), (d * d).sum(0), np.array([rows.shape[0]], np.float64)))
-    return self._publish()
-
-  def update_from_moments(self, result):
-    """The same update from a `PopulationResult`'s on-chip moments (each step
-    weighted by the env's `active`), centred on `mean_t` as the acting policy
-    read it."""
-    self.mean, self.summed_variance, self.count, self.std = update_running_statistics(
-        self.mean, self.summed_variance, self.count, result)
-    return self._publish()
-
-  def _publish(self):
-    self.mean_t.copy_(torch.as_tensor(self.mean, dtype=torch.float32))
-    self.std_t.copy_(torch.as_tensor(self.std, dtype=torch.float32))
-    return self
-
-
 def transitions(obs0: torch.Tensor, traj, extras) -> Transition:
   """One unroll as `acting.actor_step` records it (`training/acting.py:30-50`),
   leading dimensions `[B, T]` (views of the trajectory, no copies but the
@@ -104,26 +65,18 @@ def transitions(obs0: torch.Tensor, traj, extras) -> Transition:
   return t.map(lambda x: x.transpose(0, 1))
 
 
-def _detached(layers):
-  return [(w.detach(), b.detach()) for w, b in layers]
-
-
 def make_optimizer(params, learning_rate: float, fused_adam=False):
   """Adam over `params`: `torch.optim.Adam` (`fused_adam` False), or
   `optim.FusedAdam`, one launch per step (True: that or NotImplementedError;
   None: that where it applies). Both have `zero_grad` and `step`."""
-  if fused_adam is not False:
-    groups = [dict(params=params, lr=learning_rate)]
-    why = optim.supported(groups)
-    if why is None:
-      return optim.FusedAdam(groups, eps=1e-8)
-    if fused_adam is True:
-      raise NotImplementedError(f'no fused Adam: {why}')
-  return torch.optim.Adam(params, lr=learning_rate, eps=1e-8)
+  return (optim.make_adam([dict(params=params, lr=learning_rate)], fused_adam)
+          or torch.optim.Adam(params, lr=learning_rate, eps=1e-8))
 
 
-class Learner:
+class Learner(driver.GradientLearner):
   """The state of one PPO run and the three phases of a training step."""
+
+  policy_kwargs = dict(activation='swish')
 
   def __init__(self, env, num_envs: int, unroll_length: int, batch_size: int,
                num_minibatches: int, num_updates_per_batch: int, learning_rate: float = 1e-4,
@@ -163,28 +116,6 @@ class Learner:
     """(normaliser, policy layers, value layers)."""
     return self.normalizer, self.policy_layers, self.value_layers
 
-  @property
-  def _mean_std(self):
-    return None if self.normalizer is None else (self.normalizer.mean_t, self.normalizer.std_t)
-
-  def make_policy(self, params=None, deterministic: bool = False) -> MLPPolicy:
-    """`make_inference_fn`: an acting `MLPPolicy` from `params` (default: the
-    learner's current ones). It reads the normaliser's device buffers, so a
-    normaliser update reaches it without a copy."""
-    normalizer, policy_layers = (self.params if params is None else params)[:2]
-    kw = {} if normalizer is None else dict(obs_mean=normalizer.mean_t, obs_std=normalizer.std_t)
-    p = MLPPolicy(_detached(policy_layers), activation='swish', deterministic=deterministic,
-                  device=self.device, **kw)
-    if normalizer is not None:  # share, not copy
-      p.obs_mean, p.obs_std = normalizer.mean_t, normalizer.std_t
-    return p
-
-  def reset(self, key):
-    self.state = self.env.reset(key)
-    if self.state.obs.shape[0] != self.num_envs:
-      raise ValueError(f'the env holds {self.state.obs.shape[0]} envs, num_envs is {self.num_envs}')
-    return self.state
-
   def collect(self) -> Transition:
     """The unroll phase: `[batch_size * num_minibatches, unroll_length]`
     transitions from consecutive `policy_rollout` launches."""
@@ -211,7 +142,7 @@ class Learner:
     steps; returns the mean of each loss metric (device tensors)."""
     n, bs = data.reward.shape[0], self.batch_size
     A = data.action.shape[-1]
-    sums, vector = {}, None
+    sums = {}
     for _ in range(self.num_updates_per_batch):
       perm = torch.randperm(n, generator=self._gen, device=self.device)
       shuffled = data.map(lambda x, perm=perm: x[perm])
@@ -224,18 +155,10 @@ class Learner:
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.optimizer.step()
-        if getattr(metrics, 'vector', None) is not None:
-          # the fused head's four metrics are one (4,) tensor: one add, not four
-          vector = metrics.vector if vector is None else vector + metrics.vector
-        else:
-          for k, v in metrics.items():
-            sums[k] = v.detach() + sums.get(k, 0)
-    self.actor.load_(_detached(self.policy_layers))
-    steps = self.num_updates_per_batch * self.num_minibatches
-    if vector is not None:
-      for k, name in enumerate(METRICS):
-        sums[name] = vector[k] + sums.get(name, 0)
-    return {k: v / steps for k, v in sums.items()}
+        # (the fused head's four metrics are one (4,) tensor: one add, not four)
+        driver.add_metrics(sums, metrics)
+    self.actor.load_(ppo_networks.detached(self.policy_layers))
+    return driver.mean_metrics(sums, self.num_updates_per_batch * self.num_minibatches, METRICS)
 
   def training_step(self):
     data = self.collect()
@@ -287,17 +210,8 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
   acct = step_accounting(num_timesteps, num_evals, batch_size, unroll_length, num_minibatches,
                          action_repeat, num_envs)
   dev = torch.device('cuda' if device is None else device)
-  if isinstance(environment, str):
-    from brax_amd import envs  # pylint: disable=import-outside-toplevel
-    env = envs.create(environment, episode_length=episode_length, action_repeat=action_repeat,
-                      batch_size=num_envs, device=dev)
-    eval_env = environment if eval_env is None else eval_env
-  else:
-    env = environment
-    if eval_env is None:
-      if num_eval_envs != num_envs:
-        raise ValueError('a batched environment needs eval_env batched at num_eval_envs')
-      eval_env = env
+  env, eval_env = driver.make_envs(environment, eval_env, num_envs, num_eval_envs, episode_length,
+                                   action_repeat, dev)
   learner = Learner(env, num_envs, unroll_length, batch_size, num_minibatches,
                     num_updates_per_batch, learning_rate=learning_rate, entropy_cost=entropy_cost,
                     discounting=discounting, reward_scaling=reward_scaling,
@@ -307,35 +221,14 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
                     network_factory=network_factory, device=dev, fused_gae=fused_gae,
                     action_repeat=action_repeat, fused_mlp=fused_mlp, fused_head=fused_head,
                     fused_adam=fused_adam)
-  key = np.array([0, int(seed)], np.uint32)  # jax.random.PRNGKey(seed) layout
-  key_env, key_eval = wrappers.split_key(key)
-  learner.reset(key_env)
+  # jax.random.PRNGKey(seed) layout; the evaluator's key is the split's other half
+  learner.reset(wrappers.split_key(np.array([0, int(seed)], np.uint32))[0])
   eval_policy = learner.make_policy(deterministic=True) if deterministic_eval else learner.actor
-  evaluator = Evaluator(eval_env, eval_policy, num_eval_envs=num_eval_envs,
-                        episode_length=episode_length, action_repeat=action_repeat,
-                        seed=int(wrappers.key_to_seed(key_eval)) & 0x7FFFFFFF, device=dev)
-  metrics = {}
-  if num_evals > 1:
-    metrics = evaluator.run_evaluation(training_metrics={})
-    progress_fn(0, metrics)
-  training_walltime = 0.0
-  for _ in range(acct.num_evals_after_init):
-    t = time.time()
-    sums = {}
-    for _ in range(acct.num_training_steps_per_epoch):
-      for k, v in learner.training_step().items():
-        sums[k] = v + sums.get(k, 0)
-    torch.cuda.synchronize(dev)
-    epoch_training_time = time.time() - t
-    training_walltime += epoch_training_time
-    training_metrics = {
-        'training/sps': (acct.num_training_steps_per_epoch * acct.env_step_per_training_step
-                         / epoch_training_time),
-        'training/walltime': training_walltime,
-        **{f'training/{k}': v / acct.num_training_steps_per_epoch for k, v in sums.items()}}
-    if eval_policy is not learner.actor:
-      eval_policy.load_(_detached(learner.policy_layers))
-    metrics = evaluator.run_evaluation(training_metrics)
-    progress_fn(learner.env_steps, metrics)
-  assert learner.env_steps >= num_timesteps
+  evaluator = driver.make_evaluator(eval_env, eval_policy, seed, num_eval_envs, episode_length,
+                                    action_repeat, dev)
+  metrics = driver.run_epochs(
+      learner, eval_policy, evaluator, acct.num_evals_after_init,
+      acct.num_training_steps_per_epoch,
+      acct.num_training_steps_per_epoch * acct.env_step_per_training_step, num_timesteps,
+      num_evals > 1, progress_fn)
   return learner.make_policy, learner.params, metrics

@@ -22,6 +22,8 @@ import torch
 
 from brax_amd import _native, abi
 from brax_amd.envs.policy import head_scale, normal_tanh_log_prob, tanh_log_det
+from brax_amd.fused import use_kernel
+from brax_amd.system import launch
 from brax_amd.training.gae import compute_gae
 
 METRICS = ('total_loss', 'policy_loss', 'v_loss', 'entropy_loss')
@@ -118,7 +120,6 @@ def head_call(logits, baseline, bootstrap_value, data, eps, entropy_cost, discou
   the last two None unless `want_gae`. `out` may hold preallocated tensors
   under those five names (any layout the header allows), `workspace` a float32
   tensor of at least `workspace_floats(T, B)` elements, 16-byte aligned."""
-  from brax_amd.system import _stream  # pylint: disable=import-outside-toplevel
   dev = logits.device
   T, B, A = logits.shape[0], logits.shape[1], logits.shape[2] // 2
   out = dict(out or {})
@@ -141,14 +142,13 @@ def head_call(logits, baseline, bootstrap_value, data, eps, entropy_cost, discou
   seqs = [_seq(t) for t in held]
   opt = [None if t is None else _seq(t) for t in (vs, adv)]
   boot = bootstrap_value.contiguous()
-  with torch.cuda.device(dev):
-    _native.check(_native.lib().bx_ppo_head(
-        T, B, A, C.byref(seqs[0]), C.byref(seqs[1]), boot.data_ptr(), C.byref(seqs[2]),
-        C.byref(seqs[3]), C.byref(seqs[4]), C.byref(seqs[5]), C.byref(seqs[6]), C.byref(seqs[7]),
-        reward_scaling, discounting, gae_lambda, clipping_epsilon, entropy_cost, min_std,
-        int(bool(normalize_advantage)), losses.data_ptr(), C.byref(seqs[8]), C.byref(seqs[9]),
-        None if opt[0] is None else C.byref(opt[0]), None if opt[1] is None else C.byref(opt[1]),
-        workspace.data_ptr(), C.byref(nbytes), _stream(dev.index)))
+  launch(dev, 'bx_ppo_head',
+         T, B, A, C.byref(seqs[0]), C.byref(seqs[1]), boot.data_ptr(), C.byref(seqs[2]),
+         C.byref(seqs[3]), C.byref(seqs[4]), C.byref(seqs[5]), C.byref(seqs[6]), C.byref(seqs[7]),
+         reward_scaling, discounting, gae_lambda, clipping_epsilon, entropy_cost, min_std,
+         int(bool(normalize_advantage)), losses.data_ptr(), C.byref(seqs[8]), C.byref(seqs[9]),
+         None if opt[0] is None else C.byref(opt[0]), None if opt[1] is None else C.byref(opt[1]),
+         workspace.data_ptr(), C.byref(nbytes))
   del held
   return losses, dlogits, dbaseline, vs, adv
 
@@ -212,18 +212,15 @@ def ppo_head(logits, baseline, bootstrap_value, data, eps, entropy_cost: float =
   hyper = dict(entropy_cost=entropy_cost, discounting=discounting, reward_scaling=reward_scaling,
                gae_lambda=gae_lambda, clipping_epsilon=clipping_epsilon,
                normalize_advantage=normalize_advantage, min_std=min_std)
-  if fused is not False:
-    why = fused_supported(logits, baseline, bootstrap_value, data, eps)
-    if why is None:
-      # (detached here as compute_gae detaches it: the network that produced
-      # it then has no backward pass to run on a zero gradient)
-      losses = _FusedHead.apply(logits, baseline, bootstrap_value.detach(), data, eps, hyper)
-      total, parts = losses[0], losses.detach()
-      metrics = Metrics(total_loss=total, policy_loss=parts[1], v_loss=parts[2],
-                        entropy_loss=parts[3])
-      metrics.vector = parts
-      return total, metrics
-    if fused is True:
-      raise NotImplementedError(f'no fused ppo_head: {why}')
+  if use_kernel(fused, 'ppo_head',
+                lambda: fused_supported(logits, baseline, bootstrap_value, data, eps)):
+    # (detached here as compute_gae detaches it: the network that produced
+    # it then has no backward pass to run on a zero gradient)
+    losses = _FusedHead.apply(logits, baseline, bootstrap_value.detach(), data, eps, hyper)
+    total, parts = losses[0], losses.detach()
+    metrics = Metrics(total_loss=total, policy_loss=parts[1], v_loss=parts[2],
+                      entropy_loss=parts[3])
+    metrics.vector = parts
+    return total, metrics
   return _chained(logits, baseline, bootstrap_value, data, eps, fused_gae=fused_gae,
                   gae=gae, **hyper)

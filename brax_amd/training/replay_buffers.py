@@ -34,7 +34,9 @@ from typing import Dict, Mapping, Optional
 
 import torch
 
-from brax_amd import _native, abi
+from brax_amd import abi
+from brax_amd.fused import use_kernel
+from brax_amd.system import launch
 
 _M64 = (1 << 64) - 1
 
@@ -177,24 +179,18 @@ class UniformSamplingQueue:
     if n > self.capacity:
       raise ValueError('Trying to insert a batch of samples larger than the maximum replay '
                        f'size. num_samples: {n}, max replay size {self.capacity}')
-    why = None if fused is False else self._why_not_fused(tensors)
-    if fused is True and why is not None:
-      raise NotImplementedError(f'no fused insert: {why}')
+    kernel = use_kernel(fused, 'insert', lambda: self._why_not_fused(tensors))
     if n == 0:
       return self
-    if fused is False or why is not None:
+    if not kernel:
       flat = torch.cat([t.to(self.data.device, self.data.dtype) for t in tensors], dim=1)
       at = (torch.arange(n, dtype=torch.int64, device=self.data.device) + self.position) % self.capacity
       self.data.index_copy_(0, at, flat)
     else:
-      from brax_amd.system import _stream  # pylint: disable=import-outside-toplevel
       tensors = [t if t.stride(1) == 1 or t.shape[1] == 1 else t.contiguous() for t in tensors]
       src = self._descriptor(tensors)
-      dev = self.data.device
-      with torch.cuda.device(dev):
-        _native.check(_native.lib().bx_replay_insert(
-            self.data.data_ptr(), self.capacity, self.row_words, self.position, n, C.byref(src),
-            _stream(dev.index)))
+      launch(self.data.device, 'bx_replay_insert', self.data.data_ptr(), self.capacity,
+             self.row_words, self.position, n, C.byref(src))
     self.position = (self.position + n) % self.capacity
     self.size = min(self.size + n, self.capacity)
     return self
@@ -226,17 +222,18 @@ class UniformSamplingQueue:
     if indices is not None and (indices.dtype != torch.int64 or tuple(indices.shape) != (n,)
                                 or indices.device != dev or not indices.is_contiguous()):
       raise ValueError(f'indices must be a contiguous int64 ({n},) tensor on {dev}')
-    why = None if fused is False else self._why_not_fused(tensors)
-    if why is None and fused is not False and any(t.stride(1) != 1 and t.shape[1] != 1
-                                                  for t in tensors):
-      why = 'an out field whose words are not adjacent'
-    if fused is True and why is not None:
-      raise NotImplementedError(f'no fused sample: {why}')
+
+    def why_not():
+      why = self._why_not_fused(tensors)
+      if why is None and any(t.stride(1) != 1 and t.shape[1] != 1 for t in tensors):
+        why = 'an out field whose words are not adjacent'
+      return why
+    kernel = use_kernel(fused, 'sample', why_not)
     offset = self.counter & _M64
     self.counter = (self.counter + n) & _M64
     if n == 0:
       return dict(out)
-    if fused is False or why is not None:
+    if not kernel:
       idx = sample_rows(self.seed, offset, n, self.position, self.size, self.capacity, dev)
       if indices is not None:
         indices.copy_(idx)
@@ -244,11 +241,8 @@ class UniformSamplingQueue:
       for t, part in zip(tensors, torch.split(flat, list(self.fields.values()), dim=1)):
         t.copy_(part)
     else:
-      from brax_amd.system import _stream  # pylint: disable=import-outside-toplevel
       dst = self._descriptor(tensors)
-      with torch.cuda.device(dev):
-        _native.check(_native.lib().bx_replay_sample(
-            self.data.data_ptr(), self.capacity, self.row_words, self.position, self.size, n,
-            self.seed & _M64, offset, C.byref(dst),
-            None if indices is None else indices.data_ptr(), _stream(dev.index)))
+      launch(dev, 'bx_replay_sample', self.data.data_ptr(), self.capacity, self.row_words,
+             self.position, self.size, n, self.seed & _M64, offset, C.byref(dst),
+             None if indices is None else indices.data_ptr())
     return dict(out)

@@ -23,18 +23,17 @@ launch, the torch MLP and `env.step`), and `(128, 128)` or narrower acts in the
 fused launch. The noise and the results are the same by construction.
 """
 import dataclasses
-import time
 from typing import Callable, List, Mapping, Optional, Tuple
 
 import numpy as np
 import torch
 
 from brax_amd.envs import wrappers
-from brax_amd.envs.evaluator import Evaluator
-from brax_amd.envs.policy import MLPPolicy, policy_rollout
-from brax_amd.training import optim, sac_head, sac_losses, sac_networks
-from brax_amd.training.networks import Layers, parameters
-from brax_amd.training.ppo import RunningStatistics
+from brax_amd.envs.policy import policy_rollout
+from brax_amd.fused import use_kernel
+from brax_amd.training import driver, optim, sac_head, sac_losses, sac_networks
+from brax_amd.training.networks import Layers, detached, parameters
+from brax_amd.training.running_statistics import RunningStatistics
 from brax_amd.training.replay_buffers import UniformSamplingQueue, transition_fields
 
 ALPHA_LEARNING_RATE = 3e-4  # train.py:178
@@ -101,19 +100,15 @@ def init_training_state(observation_size: int, action_size: int, learning_rate: 
   policy, q = network_factory(observation_size, action_size, seed=seed, device=device, dtype=dtype)
   target = [[(w.detach().clone(), b.detach().clone()) for w, b in c] for c in q]
   log_alpha = torch.zeros((), dtype=dtype, device=device, requires_grad=True)
-  if fused_adam is not False:
-    groups = [dict(params=[log_alpha], lr=ALPHA_LEARNING_RATE),
-              dict(params=sac_networks.q_parameters(q), lr=learning_rate,
-                   targets=sac_networks.q_parameters(target), tau=tau),
-              dict(params=parameters(policy), lr=learning_rate)]
-    why = optim.supported(groups)
-    if why is None:
-      return TrainingState(policy_layers=policy, q_layers=q, target_q_layers=target,
-                           log_alpha=log_alpha, policy_optimizer=None, q_optimizer=None,
-                           alpha_optimizer=None,
-                           fused_optimizer=optim.FusedAdam(groups, eps=1e-8))
-    if fused_adam is True:
-      raise NotImplementedError(f'no fused Adam: {why}')
+  fused = optim.make_adam(
+      [dict(params=[log_alpha], lr=ALPHA_LEARNING_RATE),
+       dict(params=sac_networks.q_parameters(q), lr=learning_rate,
+            targets=sac_networks.q_parameters(target), tau=tau),
+       dict(params=parameters(policy), lr=learning_rate)], fused_adam)
+  if fused is not None:
+    return TrainingState(policy_layers=policy, q_layers=q, target_q_layers=target,
+                         log_alpha=log_alpha, policy_optimizer=None, q_optimizer=None,
+                         alpha_optimizer=None, fused_optimizer=fused)
   return TrainingState(
       policy_layers=policy, q_layers=q, target_q_layers=target, log_alpha=log_alpha,
       policy_optimizer=torch.optim.Adam(parameters(policy), lr=learning_rate, eps=1e-8),
@@ -151,13 +146,10 @@ def _chained_gradients(ts: TrainingState, normalizer, transitions, eps, reward_s
 
 
 def _gradients(ts, normalizer, transitions, eps, reward_scaling, discounting, fused_mlp, fused_head):
-  if fused_head is not False:
-    why = sac_head.fused_supported(ts, normalizer, transitions, eps)
-    if why is None:
-      return sac_head.gradients(ts, normalizer, transitions, eps, reward_scaling, discounting,
-                                fused_mlp)
-    if fused_head is True:
-      raise NotImplementedError(f'no fused sac head: {why}')
+  if use_kernel(fused_head, 'sac head',
+                lambda: sac_head.fused_supported(ts, normalizer, transitions, eps)):
+    return sac_head.gradients(ts, normalizer, transitions, eps, reward_scaling, discounting,
+                              fused_mlp)
   return _chained_gradients(ts, normalizer, transitions, eps, reward_scaling, discounting, fused_mlp)
 
 
@@ -211,12 +203,10 @@ def sgd_step(ts: TrainingState, normalizer, transitions: Mapping[str, torch.Tens
   return metrics
 
 
-def _detached(layers):
-  return [(w.detach(), b.detach()) for w, b in layers]
-
-
-class Learner:
+class Learner(driver.GradientLearner):
   """The state of one SAC run and the phases of a training step."""
+
+  policy_kwargs = dict(activation=sac_networks.ACTIVATION, min_std=sac_losses.MIN_STD)
 
   def __init__(self, env, num_envs: int, batch_size: int = 256, grad_updates_per_step: int = 1,
                max_replay_size: int = 1 << 20, num_prefill_actor_steps: int = 0,
@@ -250,27 +240,6 @@ class Learner:
     """(normaliser, policy layers), the reference's returned `params`."""
     return self.normalizer, self.ts.policy_layers
 
-  @property
-  def _mean_std(self):
-    return None if self.normalizer is None else (self.normalizer.mean_t, self.normalizer.std_t)
-
-  def make_policy(self, params=None, deterministic: bool = False) -> MLPPolicy:
-    """`make_inference_fn`: an acting `MLPPolicy` from `params` (default: the
-    learner's current ones); it shares the normaliser's device buffers."""
-    normalizer, policy_layers = (self.params if params is None else params)[:2]
-    kw = {} if normalizer is None else dict(obs_mean=normalizer.mean_t, obs_std=normalizer.std_t)
-    p = MLPPolicy(_detached(policy_layers), activation=sac_networks.ACTIVATION,
-                  min_std=sac_losses.MIN_STD, deterministic=deterministic, device=self.device, **kw)
-    if normalizer is not None:  # share, not copy
-      p.obs_mean, p.obs_std = normalizer.mean_t, normalizer.std_t
-    return p
-
-  def reset(self, key):
-    self.state = self.env.reset(key)
-    if self.state.obs.shape[0] != self.num_envs:
-      raise ValueError(f'the env holds {self.state.obs.shape[0]} envs, num_envs is {self.num_envs}')
-    return self.state
-
   def get_experience(self):
     """`get_experience` (`train.py:271-287`): one actor step, the normaliser
     update from the observation the policy read, the insert."""
@@ -303,15 +272,10 @@ class Learner:
                   for _ in range(3))
       metrics = sgd_step(self.ts, self._mean_std, mb, eps, fused_mlp=self.fused_mlp,
                          fused_head=self.fused_head, **self.loss_kwargs)
-      vector = getattr(metrics, 'vector', None)
-      if vector is not None:  # the three losses in one addition
-        metrics = {'losses': vector, 'alpha': metrics['alpha']}
-      for k, v in metrics.items():
-        sums[k] = v + sums.get(k, 0)
-    self.actor.load_(_detached(self.ts.policy_layers))
-    if 'losses' in sums:
-      sums = {**dict(zip(sac_head.METRICS, sums['losses'])), 'alpha': sums['alpha']}
-    return {k: v / self.grad_updates_per_step for k, v in sums.items()}
+      # (the fused head's three losses in one addition, alpha in another)
+      driver.add_metrics(sums, metrics)
+    self.actor.load_(detached(self.ts.policy_layers))
+    return driver.mean_metrics(sums, self.grad_updates_per_step, sac_head.METRICS)
 
   def training_step(self):
     """`training_step` (`train.py:289-313`)."""
@@ -373,17 +337,8 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
   acct = step_accounting(num_timesteps, num_evals, min_replay_size, num_envs, action_repeat,
                          max_replay_size)
   dev = torch.device('cuda' if device is None else device)
-  if isinstance(environment, str):
-    from brax_amd import envs  # pylint: disable=import-outside-toplevel
-    env = envs.create(environment, episode_length=episode_length, action_repeat=action_repeat,
-                      batch_size=num_envs, device=dev)
-    eval_env = environment if eval_env is None else eval_env
-  else:
-    env = environment
-    if eval_env is None:
-      if num_eval_envs != num_envs:
-        raise ValueError('a batched environment needs eval_env batched at num_eval_envs')
-      eval_env = env
+  env, eval_env = driver.make_envs(environment, eval_env, num_envs, num_eval_envs, episode_length,
+                                   action_repeat, dev)
   learner = Learner(env, num_envs, batch_size=batch_size,
                     grad_updates_per_step=grad_updates_per_step,
                     max_replay_size=acct.max_replay_size,
@@ -394,39 +349,18 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
                     network_factory=network_factory, device=dev, action_repeat=action_repeat,
                     fused_buffer=fused_buffer, fused_mlp=fused_mlp, fused_adam=fused_adam,
                     fused_head=fused_head)
-  key = np.array([0, int(seed)], np.uint32)  # jax.random.PRNGKey(seed) layout
-  key_env, key_eval = wrappers.split_key(key)
-  learner.reset(key_env)
+  # jax.random.PRNGKey(seed) layout; the evaluator's key is the split's other half
+  learner.reset(wrappers.split_key(np.array([0, int(seed)], np.uint32))[0])
   eval_policy = learner.make_policy(deterministic=True) if deterministic_eval else learner.actor
-  evaluator = Evaluator(eval_env, eval_policy, num_eval_envs=num_eval_envs,
-                        episode_length=episode_length, action_repeat=action_repeat,
-                        seed=int(wrappers.key_to_seed(key_eval)) & 0x7FFFFFFF, device=dev)
-  metrics = {}
-  if num_evals > 1:
-    metrics = evaluator.run_evaluation(training_metrics={})
-    progress_fn(0, metrics)
-  t = time.time()
-  learner.prefill()
-  torch.cuda.synchronize(dev)
-  assert learner.buffer.size >= min_replay_size
-  training_walltime = time.time() - t
-  for _ in range(acct.num_evals_after_init):
-    t = time.time()
-    sums = {}
-    for _ in range(acct.num_training_steps_per_epoch):
-      for k, v in learner.training_step().items():
-        sums[k] = v + sums.get(k, 0)
-    torch.cuda.synchronize(dev)
-    epoch_training_time = time.time() - t
-    training_walltime += epoch_training_time
-    training_metrics = {
-        'training/sps': (acct.env_steps_per_actor_step * acct.num_training_steps_per_epoch
-                         / epoch_training_time),
-        'training/walltime': training_walltime,
-        **{f'training/{k}': v / acct.num_training_steps_per_epoch for k, v in sums.items()}}
-    if eval_policy is not learner.actor:
-      eval_policy.load_(_detached(learner.ts.policy_layers))
-    metrics = evaluator.run_evaluation(training_metrics)
-    progress_fn(learner.env_steps, metrics)
-  assert learner.env_steps >= num_timesteps
+  evaluator = driver.make_evaluator(eval_env, eval_policy, seed, num_eval_envs, episode_length,
+                                    action_repeat, dev)
+
+  def prefill():
+    learner.prefill()
+    assert learner.buffer.size >= min_replay_size
+  metrics = driver.run_epochs(
+      learner, eval_policy, evaluator, acct.num_evals_after_init,
+      acct.num_training_steps_per_epoch,
+      acct.env_steps_per_actor_step * acct.num_training_steps_per_epoch, num_timesteps,
+      num_evals > 1, progress_fn, prefill=prefill)
   return learner.make_policy, learner.params, metrics

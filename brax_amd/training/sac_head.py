@@ -29,8 +29,9 @@ from typing import Optional
 import torch
 
 from brax_amd import _native, abi
+from brax_amd.system import launch
 from brax_amd.training import sac_losses
-from brax_amd.training.networks import mlp, parameters
+from brax_amd.training.networks import detached, mlp, parameters
 from brax_amd.training.sac_networks import ACTIVATION
 
 METRICS = ('critic_loss', 'actor_loss', 'alpha_loss')
@@ -92,11 +93,6 @@ def fused_supported(ts, normalizer, transitions, eps) -> Optional[str]:
   return None
 
 
-def _stream(dev):
-  from brax_amd.system import _stream as stream  # pylint: disable=import-outside-toplevel
-  return stream(dev.index)
-
-
 def _pitch(t):
   """The row pitch of a (B, W) tensor with unit inner stride (one row: W)."""
   return max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]
@@ -121,12 +117,11 @@ def prep_call(obs, next_obs, action, normalizer, x_cur, x_next, x_pi):
   assert _pitch(x_cur) == _pitch(x_next) == _pitch(x_pi)
   mean, std = (None, None) if normalizer is None else (normalizer[0].contiguous(),
                                                        normalizer[1].contiguous())
-  with torch.cuda.device(obs.device):
-    _native.check(_native.lib().bx_sac_head_prep(
-        B, O, A, obs.data_ptr(), _pitch(obs), next_obs.data_ptr(), _pitch(next_obs),
-        action.data_ptr(), _pitch(action), None if mean is None else mean.data_ptr(),
-        None if std is None else std.data_ptr(), x_cur.data_ptr(), x_next.data_ptr(),
-        x_pi.data_ptr(), _pitch(x_cur), _stream(obs.device)))
+  launch(obs.device, 'bx_sac_head_prep',
+         B, O, A, obs.data_ptr(), _pitch(obs), next_obs.data_ptr(), _pitch(next_obs),
+         action.data_ptr(), _pitch(action), None if mean is None else mean.data_ptr(),
+         None if std is None else std.data_ptr(), x_cur.data_ptr(), x_next.data_ptr(),
+         x_pi.data_ptr(), _pitch(x_cur))
 
 
 def sample_call(jobs, min_std=sac_losses.MIN_STD):
@@ -143,9 +138,7 @@ def sample_call(jobs, min_std=sac_losses.MIN_STD):
     if action is not None:
       j.action, j.action_pitch = action.data_ptr(), _pitch(action)
     j.log_prob = log_prob.data_ptr()
-  with torch.cuda.device(logits.device):
-    _native.check(_native.lib().bx_sac_head_sample(B, A, table, len(jobs), min_std,
-                                                   _stream(logits.device)))
+  launch(logits.device, 'bx_sac_head_sample', B, A, table, len(jobs), min_std)
 
 
 def _flag(t):
@@ -168,12 +161,11 @@ def losses_call(log_probs, q_old, next_q, q_pi, reward, discount, truncation, lo
       assert t.is_contiguous() and t.numel() == B
       getattr(q, name)[c] = t.data_ptr()
   nbytes = C.c_int64(workspace.numel() * 4)
-  with torch.cuda.device(g_lp.device):
-    _native.check(_native.lib().bx_sac_head_losses(
-        B, n, log_probs[0].data_ptr(), log_probs[1].data_ptr(), log_probs[2].data_ptr(),
-        C.byref(q), *_flag(reward), *_flag(discount), *_flag(truncation), log_alpha.data_ptr(),
-        reward_scaling, discounting, target_entropy, g_lp.data_ptr(), workspace.data_ptr(),
-        C.byref(nbytes), _stream(g_lp.device)))
+  launch(g_lp.device, 'bx_sac_head_losses',
+         B, n, log_probs[0].data_ptr(), log_probs[1].data_ptr(), log_probs[2].data_ptr(),
+         C.byref(q), *_flag(reward), *_flag(discount), *_flag(truncation), log_alpha.data_ptr(),
+         reward_scaling, discounting, target_entropy, g_lp.data_ptr(), workspace.data_ptr(),
+         C.byref(nbytes))
 
 
 def sample_backward_call(logits, eps, g_lp, dactions, dlogits, losses, dlog_alpha, workspace,
@@ -188,12 +180,10 @@ def sample_backward_call(logits, eps, g_lp, dactions, dlogits, losses, dlog_alph
   for c, t in enumerate(dactions):
     da.ptr[c], da.pitch[c] = t.data_ptr(), _pitch(t)
   nbytes = C.c_int64(workspace.numel() * 4)
-  with torch.cuda.device(logits.device):
-    _native.check(_native.lib().bx_sac_head_sample_backward(
-        B, A, len(dactions), logits.data_ptr(), _pitch(logits), eps.data_ptr(), _pitch(eps),
-        g_lp.data_ptr(), C.byref(da), min_std, dlogits.data_ptr(), _pitch(dlogits),
-        losses.data_ptr(), dlog_alpha.data_ptr(), workspace.data_ptr(), C.byref(nbytes),
-        _stream(logits.device)))
+  launch(logits.device, 'bx_sac_head_sample_backward',
+         B, A, len(dactions), logits.data_ptr(), _pitch(logits), eps.data_ptr(), _pitch(eps),
+         g_lp.data_ptr(), C.byref(da), min_std, dlogits.data_ptr(), _pitch(dlogits),
+         losses.data_ptr(), dlog_alpha.data_ptr(), workspace.data_ptr(), C.byref(nbytes))
 
 
 _BUFFERS = {}
@@ -251,8 +241,7 @@ def gradients(ts, normalizer, transitions, eps, reward_scaling: float = 1.0,
   q_old = [mlp(c, x_cur, ACTIVATION, fused_mlp) for c in ts.q_layers]
   with torch.no_grad():
     next_q = [mlp(c, x_next, ACTIVATION, fused_mlp) for c in ts.target_q_layers]
-  q_pi = [mlp([(w.detach(), b.detach()) for w, b in c], x_pi, ACTIVATION, fused_mlp)
-          for c in ts.q_layers]
+  q_pi = [mlp(detached(c), x_pi, ACTIVATION, fused_mlp) for c in ts.q_layers]
   flat = lambda ts_: [t.detach().contiguous() for t in ts_]  # noqa: E731
   losses_call(buf['log_probs'], flat(q_old), flat(next_q), flat(q_pi), transitions['reward'],
               transitions['discount'], transitions['truncation'], ts.log_alpha.detach(),
