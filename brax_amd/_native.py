@@ -25,92 +25,23 @@ def build(arch='gfx950', jobs=4):
 
 _lib = None
 
-_SIGS = {
-    'bx_abi_version': ([], C.c_int),
-    'bx_last_error': ([], C.c_char_p),
-    'bx_device_count': ([C.POINTER(C.c_int)], C.c_int),
-    'bx_system_create': ([C.POINTER(abi.BxDesc), C.POINTER(abi.BxResetDesc), C.c_int,
-                          C.POINTER(C.c_void_p)], C.c_int),
-    'bx_system_destroy': ([C.c_void_p], C.c_int),
-    'bx_system_lanes': ([C.c_void_p], C.c_int),
-    'bx_system_env_lanes': ([C.c_void_p], C.c_int),
-    'bx_system_lds_bytes': ([C.c_void_p], C.c_int),
-    'bx_system_plan': ([C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                        C.POINTER(C.c_int32)], C.c_int),
-    'bx_system_blob': abi.SIGNATURES['bx_system_blob'],
-    'bx_system_set_single': ([C.c_void_p, C.c_int], C.c_int),
-    'bx_system_set_variant': ([C.c_void_p, C.c_int, C.c_int], C.c_int),
-    'bx_system_set_block': ([C.c_void_p, C.c_int], C.c_int),
-    'bx_system_step': ([C.c_void_p, C.c_int64, C.POINTER(abi.BxQP), C.c_void_p, C.c_int64,
-                        C.c_int64, C.POINTER(abi.BxQP), C.POINTER(abi.BxInfo), C.c_void_p],
-                       C.c_int),
-    'bx_env_step': ([C.c_void_p, C.POINTER(abi.BxEnvParams), C.c_int64,
-                     C.POINTER(abi.BxEnvState), C.c_void_p, C.c_int64, C.c_int64,
-                     C.POINTER(abi.BxEnvState), C.c_void_p], C.c_int),
-    'bx_env_step_packed': ([C.c_void_p, C.POINTER(abi.BxEnvParams), C.c_int64, C.c_void_p,
-                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
-                            C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-    'bx_env_rollout_packed': ([C.c_void_p, C.POINTER(abi.BxEnvParams), C.c_int64, C.c_int32,
-                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                               C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                               C.c_void_p], C.c_int),
-    'bx_env_rollout_random': ([C.c_void_p, C.POINTER(abi.BxEnvParams), C.c_int64, C.c_int32,
-                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
-                               C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_int64,
-                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-    'bx_env_sizes': ([C.c_void_p, C.POINTER(abi.BxEnvParams), C.POINTER(C.c_int32),
-                      C.POINTER(C.c_int32)], C.c_int),
-    'bx_env_reset': ([C.c_void_p, C.POINTER(abi.BxEnvParams), C.c_int64, C.c_uint64, C.c_int64,
-                      C.c_void_p, C.c_float, C.POINTER(abi.BxEnvState), C.c_void_p], C.c_int),
-    'bx_system_default_qp': ([C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                              C.POINTER(abi.BxQP), C.c_void_p], C.c_int),
-    'bx_system_info': ([C.c_void_p, C.c_int64, C.POINTER(abi.BxQP), C.POINTER(abi.BxInfo),
-                        C.c_void_p], C.c_int),
-    'bx_env_observe': ([C.c_void_p, C.POINTER(abi.BxEnvParams), C.c_int64,
-                        C.POINTER(abi.BxQP), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
-                        C.c_void_p], C.c_int),
-    'bx_system_joint_angles': ([C.c_void_p, C.c_int64, C.POINTER(abi.BxQP), C.c_void_p,
-                                C.c_void_p, C.c_void_p], C.c_int),
-    'bx_phase': ([C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                  C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
-    'bx_phase_capsule_plane': ([C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                C.c_int64, C.c_void_p], C.c_int),
-    'bx_debug_stamps': ([C.POINTER(C.c_ulonglong), C.c_int], C.c_int),
-    'bx_debug_partner': ([C.c_void_p, C.c_int, C.c_void_p], C.c_int),
-    'bx_uniform': ([C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
-                    C.c_void_p], C.c_int),
-    'bx_uniform_epoch': ([C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p,
-                          C.c_uint64, C.c_float, C.c_float, C.c_void_p], C.c_int),
-    'bx_uniform_slabs': ([C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64,
-                          C.c_void_p, C.c_uint64, C.c_float, C.c_float, C.c_void_p], C.c_int),
-    'bx_normal_slabs': ([C.c_void_p, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64,
-                         C.c_void_p, C.c_uint64, C.c_void_p], C.c_int),
-    'bx_env_rollout_policy': ([C.c_void_p, C.POINTER(abi.BxEnvParams), C.c_int64, C.c_int32,
-                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                               C.POINTER(abi.BxPolicy), C.c_uint64, C.c_uint64, C.c_uint64,
-                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                               C.c_void_p], C.c_int),
-    'bx_env_eval_policy': abi.SIGNATURES['bx_env_eval_policy'],
-    'bx_env_eval_packed': abi.SIGNATURES['bx_env_eval_packed'],
-    'bx_env_eval_population': abi.SIGNATURES['bx_env_eval_population'],
-    'bx_compute_gae': abi.SIGNATURES['bx_compute_gae'],
-    'bx_population_perturb': abi.SIGNATURES['bx_population_perturb'],
-    'bx_population_delta': abi.SIGNATURES['bx_population_delta'],
-    'bx_replay_insert': abi.SIGNATURES['bx_replay_insert'],
-    'bx_replay_sample': abi.SIGNATURES['bx_replay_sample'],
-    'bx_mlp_sizes': abi.SIGNATURES['bx_mlp_sizes'],
-    'bx_mlp_forward': abi.SIGNATURES['bx_mlp_forward'],
-    'bx_mlp_backward': abi.SIGNATURES['bx_mlp_backward'],
-    'bx_ppo_head': abi.SIGNATURES['bx_ppo_head'],
-    'bx_sac_head_prep': abi.SIGNATURES['bx_sac_head_prep'],
-    'bx_sac_head_sample': abi.SIGNATURES['bx_sac_head_sample'],
-    'bx_sac_head_losses': abi.SIGNATURES['bx_sac_head_losses'],
-    'bx_sac_head_sample_backward': abi.SIGNATURES['bx_sac_head_sample_backward'],
-    'bx_opt_sizes': abi.SIGNATURES['bx_opt_sizes'],
-    'bx_adam_step': abi.SIGNATURES['bx_adam_step'],
-}
-
+_SIGS = abi.SIGNATURES  # name -> (argtypes, restype), from the one table abi.ARGS
 EXPORTS = tuple(_SIGS)
+# what an argument nobody names is: a null pointer, a zero scalar
+_UNNAMED = {name: tuple(0 if issubclass(t, C._SimpleCData) and t is not C.c_void_p else None
+                        for _, t in sig) for name, sig in abi.ARGS.items()}
+
+
+def args(entry, **named):
+  """The positional arguments of the entry point `entry`, in the header's
+  order, from the ones given by name; the others are NULL or 0 (what its
+  zero-step probes and optional outputs mean). A name the entry point does not
+  have is a TypeError, as a repeated one is for any call."""
+  sig = abi.ARGS[entry]
+  unknown = named.keys() - {n for n, _ in sig}
+  if unknown:
+    raise TypeError(f'{entry} has no argument {sorted(unknown)}')
+  return tuple(named.get(n, d) for (n, _), d in zip(sig, _UNNAMED[entry]))
 
 
 def lib():

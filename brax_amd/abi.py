@@ -1,4 +1,5 @@
-"""ctypes mirror of `include/brax_amd.h` (structs only, no library loading).
+"""ctypes mirror of `include/brax_amd.h`: its structs, its constants and every
+entry point's signature (`ARGS`); no library loading.
 
 `make_desc` / `make_reset_desc` turn the compiler's numpy descriptor into the
 C structs; the returned keep-alive list must outlive every call that reads the
@@ -109,23 +110,6 @@ class BxPolicy(C.Structure):
               ('deterministic', C.c_int32), ('action_size', C.c_int32)]
 
 
-# The evaluation entry points, argument by argument in the header's order
-# (name, ctypes type); `eval_in` / `eval_out` are (M + 3, B) float32: the M
-# metric sums in the env's metric order, the reward sum, active_episodes,
-# episode_steps.
-_vp = C.c_void_p
-EVAL_POLICY_ARGS = (
-    ('sys', _vp), ('env', C.POINTER(BxEnvParams)), ('n_envs', C.c_int64), ('n_steps', C.c_int32),
-    ('qp_in', _vp), ('obs_in', _vp), ('done_in', _vp), ('steps_in', _vp), ('rng_in', _vp),
-    ('policy', C.POINTER(BxPolicy)), ('seed', C.c_uint64), ('offset', C.c_uint64),
-    ('step_stride', C.c_uint64), ('eval_in', _vp), ('out', _vp), ('eval_out', _vp),
-    ('rng_out', _vp), ('stream', _vp))
-EVAL_PACKED_ARGS = (
-    ('sys', _vp), ('env', C.POINTER(BxEnvParams)), ('n_envs', C.c_int64), ('n_steps', C.c_int32),
-    ('qp_in', _vp), ('done_in', _vp), ('steps_in', _vp), ('rng_in', _vp), ('act', _vp),
-    ('act_stride', C.c_int64), ('act_step_stride', C.c_int64), ('act_width', C.c_int64),
-    ('eval_in', _vp), ('out', _vp), ('eval_out', _vp), ('rng_out', _vp), ('stream', _vp))
-
 HEADS = {'normal_tanh': 0, 'identity': 1}  # BX_HEAD_NORMAL_TANH / BX_HEAD_IDENTITY
 POP_NO_STAGE = 1  # BX_POP_NO_STAGE
 
@@ -136,32 +120,13 @@ class BxPopulation(C.Structure):
               ('staged', C.c_int32), ('lds_bytes', C.c_int32)]
 
 
-# bx_env_eval_population: bx_env_eval_policy's arguments, then the population
-# struct before the stream
-EVAL_POPULATION_ARGS = EVAL_POLICY_ARGS[:-1] + (('pop', C.POINTER(BxPopulation)), ('stream', _vp))
-
-
 class BxSeq(C.Structure):
   """One float32 (T, B) array: element (t, e) at ptr[t * time_stride + e *
   env_stride], strides in elements."""
   _fields_ = [('ptr', C.c_void_p), ('time_stride', C.c_int64), ('env_stride', C.c_int64)]
 
 
-_seq = C.POINTER(BxSeq)
-COMPUTE_GAE_ARGS = (
-    ('n_steps', C.c_int64), ('n_envs', C.c_int64), ('reward', _seq), ('done', _seq),
-    ('truncation', _seq), ('values', _seq), ('bootstrap', _vp), ('vs', _seq),
-    ('advantages', _seq), ('reward_scaling', C.c_float), ('discount', C.c_float),
-    ('lambda', C.c_float), ('stream', _vp))
 POPULATION_DELTA_CHUNK = 64  # BX_POPULATION_DELTA_CHUNK
-POPULATION_PERTURB_ARGS = (
-    ('rows', _vp), ('theta', _vp), ('n_directions', C.c_int64), ('n_params', C.c_int64),
-    ('stride', C.c_int64), ('sigma', C.c_double), ('seed', C.c_uint64), ('offset', C.c_uint64),
-    ('antithetic', C.c_int), ('frozen', _vp), ('stream', _vp))
-POPULATION_DELTA_ARGS = (
-    ('out', _vp), ('weights', _vp), ('n_directions', C.c_int64), ('n_params', C.c_int64),
-    ('seed', C.c_uint64), ('offset', C.c_uint64), ('frozen', _vp), ('workspace', _vp),
-    ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
 FIELDS_MAX = 8  # BX_FIELDS_MAX
 
 
@@ -172,14 +137,6 @@ class BxFields(C.Structure):
               ('width', C.c_int64 * FIELDS_MAX), ('row_stride', C.c_int64 * FIELDS_MAX)]
 
 
-_fields = C.POINTER(BxFields)
-REPLAY_INSERT_ARGS = (
-    ('data', _vp), ('capacity', C.c_int64), ('row_words', C.c_int64), ('position', C.c_int64),
-    ('n_rows', C.c_int64), ('src', _fields), ('stream', _vp))
-REPLAY_SAMPLE_ARGS = (
-    ('data', _vp), ('capacity', C.c_int64), ('row_words', C.c_int64), ('position', C.c_int64),
-    ('size', C.c_int64), ('n_samples', C.c_int64), ('seed', C.c_uint64), ('offset', C.c_uint64),
-    ('dst', _fields), ('idx_out', _vp), ('stream', _vp))
 MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_IN = 8, 256, 1024  # BX_MLP_MAX_*
 
 
@@ -197,26 +154,7 @@ class BxMlpGrads(C.Structure):
   _fields_ = [('dw', C.c_void_p * MLP_MAX_LAYERS), ('db', C.c_void_p * MLP_MAX_LAYERS)]
 
 
-_mlp = C.POINTER(BxMlp)
-MLP_SIZES_ARGS = (('mlp_bytes', C.POINTER(C.c_int32)), ('grads_bytes', C.POINTER(C.c_int32)))
-MLP_FORWARD_ARGS = (
-    ('net', _mlp), ('rows', C.c_int64), ('x', _vp), ('x_stride', C.c_int64), ('y', _vp),
-    ('saved', _vp), ('stream', _vp))
-MLP_BACKWARD_ARGS = (
-    ('net', _mlp), ('rows', C.c_int64), ('x', _vp), ('x_stride', C.c_int64), ('saved', _vp),
-    ('dy', _vp), ('dx', _vp), ('grads', C.POINTER(BxMlpGrads)), ('workspace', _vp),
-    ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
-# bx_ppo_head: the (T, B, W) arrays are BxSeq with unit stride along a row
-PPO_HEAD_BLOCK = 256  # envs of a scan workgroup, rows of a row workgroup
-PPO_HEAD_ARGS = (
-    ('n_steps', C.c_int64), ('n_envs', C.c_int64), ('n_actions', C.c_int64), ('logits', _seq),
-    ('baseline', _seq), ('bootstrap', _vp), ('raw_action', _seq), ('eps', _seq),
-    ('log_prob', _seq), ('reward', _seq), ('done', _seq), ('truncation', _seq),
-    ('reward_scaling', C.c_float), ('discount', C.c_float), ('lambda', C.c_float),
-    ('clipping_epsilon', C.c_double), ('entropy_cost', C.c_float), ('min_std', C.c_float),
-    ('normalize_advantage', C.c_int), ('losses', _vp), ('dlogits', _seq), ('dbaseline', _seq),
-    ('vs', _seq), ('advantages', _seq), ('workspace', _vp),
-    ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
+PPO_HEAD_BLOCK = 256  # bx_ppo_head: envs of a scan workgroup, rows of a row workgroup
 # bx_sac_head_*: the SAC loss heads, one entry point per launch
 SAC_MAX_CRITICS, SAC_MAX_JOBS = 4, 3  # BX_SAC_MAX_CRITICS / BX_SAC_MAX_JOBS
 SAC_HEAD_BLOCK = 256  # rows of a workgroup
@@ -243,27 +181,6 @@ class BxSacDaction(C.Structure):
   _fields_ = [('ptr', C.c_void_p * SAC_MAX_CRITICS), ('pitch', C.c_int64 * SAC_MAX_CRITICS)]
 
 
-SAC_HEAD_PREP_ARGS = (
-    ('n_rows', C.c_int64), ('n_obs', C.c_int64), ('n_actions', C.c_int64), ('obs', _vp),
-    ('obs_pitch', C.c_int64), ('next_obs', _vp), ('next_obs_pitch', C.c_int64), ('action', _vp),
-    ('action_pitch', C.c_int64), ('mean', _vp), ('std', _vp), ('x_cur', _vp), ('x_next', _vp),
-    ('x_pi', _vp), ('x_pitch', C.c_int64), ('stream', _vp))
-SAC_HEAD_SAMPLE_ARGS = (
-    ('n_rows', C.c_int64), ('n_actions', C.c_int64), ('jobs', C.POINTER(BxSacSampleJob)),
-    ('n_jobs', C.c_int32), ('min_std', C.c_float), ('stream', _vp))
-SAC_HEAD_LOSSES_ARGS = (
-    ('n_rows', C.c_int64), ('n_critics', C.c_int32), ('lp_alpha', _vp), ('lp_next', _vp),
-    ('lp_pi', _vp), ('q', C.POINTER(BxSacQ)), ('reward', _vp), ('reward_stride', C.c_int64),
-    ('discount', _vp), ('discount_stride', C.c_int64), ('truncation', _vp),
-    ('truncation_stride', C.c_int64), ('log_alpha', _vp), ('reward_scaling', C.c_float),
-    ('discounting', C.c_float), ('target_entropy', C.c_float), ('g_lp', _vp), ('workspace', _vp),
-    ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
-SAC_HEAD_SAMPLE_BACKWARD_ARGS = (
-    ('n_rows', C.c_int64), ('n_actions', C.c_int64), ('n_critics', C.c_int32), ('logits', _vp),
-    ('logits_pitch', C.c_int64), ('eps', _vp), ('eps_pitch', C.c_int64), ('g_lp', _vp),
-    ('da', C.POINTER(BxSacDaction)), ('min_std', C.c_float), ('dlogits', _vp),
-    ('dlogits_pitch', C.c_int64), ('losses', _vp), ('dlog_alpha', _vp), ('workspace', _vp),
-    ('workspace_bytes', C.POINTER(C.c_int64)), ('stream', _vp))
 OPT_MAX_TENSORS = 32  # BX_OPT_MAX_TENSORS
 OPT_CHUNK = 1024  # elements of one tensor that one workgroup of bx_adam_step owns
 
@@ -275,27 +192,134 @@ class BxOptTensor(C.Structure):
               ('target', C.c_void_p), ('n', C.c_int64), ('lr', C.c_float), ('tau', C.c_float)]
 
 
-OPT_SIZES_ARGS = (('tensor_bytes', C.POINTER(C.c_int32)),)
-ADAM_STEP_ARGS = (
-    ('t', C.POINTER(BxOptTensor)), ('n_tensors', C.c_int32), ('step', C.c_int64),
-    ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_float), ('stream', _vp))
 PLAN_FIELDS = ('mode', 'lanes', 'lds_bytes', 'feat', 'gw', 'fold', 'jb', 'cb')  # bx_system_blob
-SYSTEM_BLOB_ARGS = (
-    ('desc', _vp), ('reset', _vp), ('words', C.POINTER(C.c_uint32)), ('capacity', C.c_int64),
-    ('n_words', C.POINTER(C.c_int64)), ('plan', C.POINTER(C.c_int32)))
-ARGS = {'bx_system_blob': SYSTEM_BLOB_ARGS,
-        'bx_env_eval_policy': EVAL_POLICY_ARGS, 'bx_env_eval_packed': EVAL_PACKED_ARGS,
-        'bx_env_eval_population': EVAL_POPULATION_ARGS, 'bx_compute_gae': COMPUTE_GAE_ARGS,
-        'bx_population_perturb': POPULATION_PERTURB_ARGS,
-        'bx_population_delta': POPULATION_DELTA_ARGS,
-        'bx_replay_insert': REPLAY_INSERT_ARGS, 'bx_replay_sample': REPLAY_SAMPLE_ARGS,
-        'bx_mlp_sizes': MLP_SIZES_ARGS, 'bx_mlp_forward': MLP_FORWARD_ARGS,
-        'bx_mlp_backward': MLP_BACKWARD_ARGS, 'bx_ppo_head': PPO_HEAD_ARGS,
-        'bx_sac_head_prep': SAC_HEAD_PREP_ARGS, 'bx_sac_head_sample': SAC_HEAD_SAMPLE_ARGS,
-        'bx_sac_head_losses': SAC_HEAD_LOSSES_ARGS,
-        'bx_sac_head_sample_backward': SAC_HEAD_SAMPLE_BACKWARD_ARGS,
-        'bx_opt_sizes': OPT_SIZES_ARGS, 'bx_adam_step': ADAM_STEP_ARGS}
-SIGNATURES = {name: ([t for _, t in args], C.c_int) for name, args in ARGS.items()}
+
+
+def _sig(*args):
+  """One entry point's (name, ctype) pairs; a bare name is a `c_void_p`: a
+  device array, the system handle or the stream."""
+  return tuple((a, C.c_void_p) if isinstance(a, str) else a for a in args)
+
+
+_ptr = C.POINTER
+_int, _i32, _i64, _u64, _f32, _f64 = C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
+_seq, _qp, _state, _fields = _ptr(BxSeq), _ptr(BxQP), _ptr(BxEnvState), _ptr(BxFields)
+_bytes = ('workspace', ('workspace_bytes', _ptr(_i64)))
+_host = (('desc', _ptr(BxDesc)), ('reset', _ptr(BxResetDesc)))
+_env = ('sys', ('env', _ptr(BxEnvParams)), ('n_envs', _i64))
+_act = ('act', ('act_stride', _i64))
+# what every K-step launch starts with (the closed-loop ones read obs_in too)
+# and how each kind names its actions: given, drawn, or the policy's
+_open = _env + (('n_steps', _i32), 'qp_in', 'done_in', 'steps_in', 'rng_in')
+_closed = _env + (('n_steps', _i32), 'qp_in', 'obs_in', 'done_in', 'steps_in', 'rng_in')
+_given = _act + (('act_step_stride', _i64), ('act_width', _i64))
+_draw = (('seed', _u64), ('offset', _u64), ('step_stride', _u64))
+_policy = (('policy', _ptr(BxPolicy)),) + _draw
+# `eval_in` / `eval_out` are (M + 3, B) float32: the M metric sums in the env's
+# metric order, the reward sum, active_episodes, episode_steps
+_eval = ('eval_in', 'out', 'eval_out', 'rng_out')
+_slabs = ('out', ('slab_n', _i64), ('n_slabs', _i64), ('seed', _u64), ('offset', _u64),
+          ('slab_stride', _u64), 'epoch', ('epoch_stride', _u64))
+_gae = (('reward', _seq), ('done', _seq), ('truncation', _seq))
+_scales = (('reward_scaling', _f32), ('discount', _f32), ('lambda', _f32))
+_ring = ('data', ('capacity', _i64), ('row_words', _i64), ('position', _i64))
+_mlp = (('net', _ptr(BxMlp)), ('rows', _i64), 'x', ('x_stride', _i64))
+
+# Every entry point of the header, argument by argument in its order: the one
+# table the loader, `_native.args` and tests/test_abi.py read. (The learner
+# heads' (T, B, W) arrays are BxSeq with unit stride along a row.)
+ARGS = {
+    'bx_abi_version': (), 'bx_last_error': (), 'bx_device_count': _sig(('count', _ptr(_int))),
+    'bx_system_create': _sig(*_host, ('device', _int), ('out', _ptr(C.c_void_p))),
+    'bx_system_destroy': _sig('sys'), 'bx_system_lanes': _sig('sys'),
+    'bx_system_env_lanes': _sig('sys'),
+    'bx_system_plan': _sig(*_host, ('mode', _ptr(_i32)), ('lanes', _ptr(_i32)),
+                           ('lds_bytes', _ptr(_i32))),
+    'bx_system_blob': _sig(*_host, ('words', _ptr(C.c_uint32)), ('capacity', _i64),
+                           ('n_words', _ptr(_i64)), ('plan', _ptr(_i32))),
+    'bx_system_lds_bytes': _sig('sys'), 'bx_system_set_single': _sig('sys', ('on', _int)),
+    'bx_system_set_variant': _sig('sys', ('lanes', _int), ('mode', _int)),
+    'bx_system_set_block': _sig('sys', ('threads', _int)),
+    'bx_system_step': _sig('sys', ('n_envs', _i64), ('qp_in', _qp), *_act, ('act_width', _i64),
+                           ('qp_out', _qp), ('info', _ptr(BxInfo)), 'stream'),
+    'bx_env_step': _sig(*_env, ('in', _state), *_act, ('act_width', _i64), ('out', _state),
+                        'stream'),
+    'bx_env_step_packed': _sig(*_env, 'qp_in', 'done_in', 'steps_in', 'rng_in', *_act,
+                               ('act_width', _i64), 'out', 'rng_out', 'stream'),
+    'bx_env_rollout_packed': _sig(*_open, *_given, 'out', 'rng_out', 'stream'),
+    'bx_env_rollout_random': _sig(*_open, *_draw, ('lo', _f32), ('hi', _f32), ('act_width', _i64),
+                                  'act_out', 'out', 'rng_out', 'stream'),
+    'bx_env_rollout_policy': _sig(*_closed, *_policy, 'act_out', 'raw_out', 'logp_out', 'out',
+                                  'rng_out', 'stream'),
+    'bx_env_eval_policy': _sig(*_closed, *_policy, *_eval, 'stream'),
+    'bx_env_eval_packed': _sig(*_open, *_given, *_eval, 'stream'),
+    # bx_env_eval_policy's arguments, then the population struct before the stream
+    'bx_env_eval_population': _sig(*_closed, *_policy, *_eval, ('pop', _ptr(BxPopulation)),
+                                   'stream'),
+    'bx_system_default_qp': _sig('sys', ('n_envs', _i64), 'joint_angle', 'joint_velocity',
+                                 ('qp_out', _qp), 'stream'),
+    'bx_system_info': _sig('sys', ('n_envs', _i64), ('qp', _qp), ('info', _ptr(BxInfo)), 'stream'),
+    'bx_env_sizes': _sig(*_env[:2], ('obs_size', _ptr(_i32)), ('n_metrics', _ptr(_i32))),
+    'bx_env_reset': _sig(*_env, ('seed', _u64), ('env_offset', _i64), 'env_seeds',
+                         ('noise_scale', _f32), ('out', _state), 'stream'),
+    'bx_env_observe': _sig(*_env, ('qp', _qp), *_act, ('act_width', _i64), 'obs', 'stream'),
+    'bx_system_joint_angles': _sig('sys', ('n_envs', _i64), ('qp', _qp), 'angle', 'vel', 'stream'),
+    'bx_uniform': _sig('out', ('n', _i64), ('seed', _u64), ('offset', _u64), ('lo', _f32),
+                       ('hi', _f32), 'stream'),
+    'bx_uniform_epoch': _sig('out', ('n', _i64), ('seed', _u64), ('offset', _u64), 'epoch',
+                             ('epoch_stride', _u64), ('lo', _f32), ('hi', _f32), 'stream'),
+    'bx_uniform_slabs': _sig(*_slabs, ('lo', _f32), ('hi', _f32), 'stream'),
+    'bx_normal_slabs': _sig(*_slabs, 'stream'),
+    'bx_compute_gae': _sig(('n_steps', _i64), ('n_envs', _i64), *_gae, ('values', _seq),
+                           'bootstrap', ('vs', _seq), ('advantages', _seq), *_scales, 'stream'),
+    'bx_population_perturb': _sig('rows', 'theta', ('n_directions', _i64), ('n_params', _i64),
+                                  ('stride', _i64), ('sigma', _f64), ('seed', _u64),
+                                  ('offset', _u64), ('antithetic', _int), 'frozen', 'stream'),
+    'bx_population_delta': _sig('out', 'weights', ('n_directions', _i64), ('n_params', _i64),
+                                ('seed', _u64), ('offset', _u64), 'frozen', *_bytes, 'stream'),
+    'bx_replay_insert': _sig(*_ring, ('n_rows', _i64), ('src', _fields), 'stream'),
+    'bx_replay_sample': _sig(*_ring, ('size', _i64), ('n_samples', _i64), ('seed', _u64),
+                             ('offset', _u64), ('dst', _fields), 'idx_out', 'stream'),
+    'bx_mlp_sizes': _sig(('mlp_bytes', _ptr(_i32)), ('grads_bytes', _ptr(_i32))),
+    'bx_mlp_forward': _sig(*_mlp, 'y', 'saved', 'stream'),
+    'bx_mlp_backward': _sig(*_mlp, 'saved', 'dy', 'dx', ('grads', _ptr(BxMlpGrads)), *_bytes,
+                            'stream'),
+    'bx_ppo_head': _sig(
+        ('n_steps', _i64), ('n_envs', _i64), ('n_actions', _i64), ('logits', _seq),
+        ('baseline', _seq), 'bootstrap', ('raw_action', _seq), ('eps', _seq), ('log_prob', _seq),
+        *_gae, *_scales, ('clipping_epsilon', _f64), ('entropy_cost', _f32), ('min_std', _f32),
+        ('normalize_advantage', _int), 'losses', ('dlogits', _seq), ('dbaseline', _seq),
+        ('vs', _seq), ('advantages', _seq), *_bytes, 'stream'),
+    'bx_opt_sizes': _sig(('tensor_bytes', _ptr(_i32))),
+    'bx_adam_step': _sig(('t', _ptr(BxOptTensor)), ('n_tensors', _i32), ('step', _i64),
+                         ('beta1', _f64), ('beta2', _f64), ('eps', _f32), 'stream'),
+    'bx_sac_head_prep': _sig(
+        ('n_rows', _i64), ('n_obs', _i64), ('n_actions', _i64), 'obs', ('obs_pitch', _i64),
+        'next_obs', ('next_obs_pitch', _i64), 'action', ('action_pitch', _i64), 'mean', 'std',
+        'x_cur', 'x_next', 'x_pi', ('x_pitch', _i64), 'stream'),
+    'bx_sac_head_sample': _sig(('n_rows', _i64), ('n_actions', _i64),
+                               ('jobs', _ptr(BxSacSampleJob)), ('n_jobs', _i32),
+                               ('min_std', _f32), 'stream'),
+    'bx_sac_head_losses': _sig(
+        ('n_rows', _i64), ('n_critics', _i32), 'lp_alpha', 'lp_next', 'lp_pi', ('q', _ptr(BxSacQ)),
+        'reward', ('reward_stride', _i64), 'discount', ('discount_stride', _i64), 'truncation',
+        ('truncation_stride', _i64), 'log_alpha', ('reward_scaling', _f32), ('discounting', _f32),
+        ('target_entropy', _f32), 'g_lp', *_bytes, 'stream'),
+    'bx_sac_head_sample_backward': _sig(
+        ('n_rows', _i64), ('n_actions', _i64), ('n_critics', _i32), 'logits',
+        ('logits_pitch', _i64), 'eps', ('eps_pitch', _i64), 'g_lp', ('da', _ptr(BxSacDaction)),
+        ('min_std', _f32), 'dlogits', ('dlogits_pitch', _i64), 'losses', 'dlog_alpha', *_bytes,
+        'stream'),
+    'bx_phase': _sig('sys', ('which', _int), ('n_envs', _i64), ('plane', _i64), 'in', 'out', 'aux',
+                     ('aux_plane', _i64), 'stream'),
+    'bx_phase_capsule_plane': _sig('sys', ('n_envs', _i64), ('plane', _i64), 'in', 'out',
+                                   ('out_plane', _i64), 'stream'),
+    'bx_debug_stamps': _sig(('out16', _ptr(C.c_ulonglong)), ('reset', _int)),
+    'bx_debug_partner': _sig('out64', ('lanes', _int), 'stream'),
+}
+# name -> (argtypes, restype): 0 on success everywhere but the message itself
+SIGNATURES = {name: ([t for _, t in args], C.c_char_p if name == 'bx_last_error' else C.c_int)
+              for name, args in ARGS.items()}
 
 
 def _arr(x, dtype):

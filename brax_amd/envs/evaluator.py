@@ -20,14 +20,13 @@ from typing import Optional
 import numpy as np
 import torch
 
-from brax_amd import _native, abi
+from brax_amd import abi
 from brax_amd.base import pack_qp
 from brax_amd.envs import packed, wrappers
 from brax_amd.envs.env import State
 from brax_amd.envs.policy import MLPPolicy, fused_supported, step_noise
 from brax_amd.envs.rollout import chain_options
 from brax_amd.fused import use_kernel
-from brax_amd.system import _stream
 
 
 def eval_keys(metric_keys):
@@ -80,15 +79,13 @@ def eval_supported(env, policy=None) -> Optional[str]:
   except NotImplementedError as e:
     return str(e)
   if policy is None:
-    return packed.refusal(u, opts, 'bx_env_eval_packed', 0, 0, None, None, None, None, None, 0, 0,
-                          u.action_size, None, None, None, None, None)
+    return packed.refusal(u, opts, 'bx_env_eval_packed', act_width=u.action_size)
   desc = policy.descriptor(u.action_size)
   if policy.head != 'normal_tanh':
     pop = abi.BxPopulation(head=abi.HEADS[policy.head])
-    return packed.refusal(u, opts, 'bx_env_eval_population', 0, 0, None, None, None, None, None,
-                          C.byref(desc), 0, 0, 0, None, None, None, None, C.byref(pop), None)
-  return packed.refusal(u, opts, 'bx_env_eval_policy', 0, 0, None, None, None, None, None,
-                        C.byref(desc), 0, 0, 0, None, None, None, None, None)
+    return packed.refusal(u, opts, 'bx_env_eval_population', policy=C.byref(desc),
+                          pop=C.byref(pop))
+  return packed.refusal(u, opts, 'bx_env_eval_policy', policy=C.byref(desc))
 
 
 def eval_rollout(env, state: State, k: Optional[int] = None, policy: Optional[MLPPolicy] = None,
@@ -138,7 +135,7 @@ def eval_rollout(env, state: State, k: Optional[int] = None, policy: Optional[ML
   dev = u.sys.device
   qbuf = pack_qp(state.qp, dev)
   B, A = qbuf.shape[0], u.action_size
-  p, done_in, steps_in, rng_in = packed.step_inputs(u, opts, state, B)
+  inputs = packed.step_inputs(u, opts, state, B)
   keys = tuple(u.metric_keys)
   M = len(keys)
   ev = pack_eval_metrics(em_in, keys, dev)
@@ -147,42 +144,22 @@ def eval_rollout(env, state: State, k: Optional[int] = None, policy: Optional[ML
   lay = packed.layout(u, B)
   out = lay.out_buffer(out, 1, dev)
   if eval_out is not None:
-    if (tuple(eval_out.shape) != (M + 3, B) or eval_out.dtype != torch.float32
-        or not eval_out.is_contiguous() or eval_out.device != dev):
-      raise ValueError(f'eval_out must be contiguous float32 ({M + 3}, {B}) on {dev}')
-    ev = eval_out.copy_(ev)
-  rng_out = torch.empty((B,), dtype=torch.int32, device=dev) if rng_in is not None else None
-  ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-  lib = _native.lib()
+    ev = packed.output_buffer('eval_out', eval_out, (M + 3, B), dev).copy_(ev)
   if policy is not None:
     stride = 2 * B * A if step_stride is None else int(step_stride)
-    obs_in = packed.obs_input(u, state, B)
-    desc = policy.descriptor(A)
+    entry = 'bx_env_eval_policy'
+    own = dict(obs_in=packed.obs_input(u, state, B), policy=C.byref(policy.descriptor(A)),
+               seed=seed, offset=offset, step_stride=stride)
     if policy.head != 'normal_tanh':
       # ARS's policy: the population kernel with one shared row, no moments
-      pop = abi.BxPopulation(head=abi.HEADS[policy.head])
-      _native.check(lib.bx_env_eval_population(
-          u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), obs_in.data_ptr(), done_in.data_ptr(),  # pylint: disable=protected-access
-          ptr(steps_in), ptr(rng_in), C.byref(desc), seed, offset, stride, ev.data_ptr(),
-          out.data_ptr(), ev.data_ptr(), ptr(rng_out), C.byref(pop), _stream(dev.index)))
-    else:
-      _native.check(lib.bx_env_eval_policy(
-          u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), obs_in.data_ptr(), done_in.data_ptr(),  # pylint: disable=protected-access
-          ptr(steps_in), ptr(rng_in), C.byref(desc), seed, offset, stride, ev.data_ptr(),
-          out.data_ptr(), ev.data_ptr(), ptr(rng_out), _stream(dev.index)))
+      entry = 'bx_env_eval_population'
+      own['pop'] = C.byref(abi.BxPopulation(head=abi.HEADS[policy.head]))
   else:
-    act = actions
-    if type(act) is not torch.Tensor or act.dtype != torch.float32 or act.device != dev:
-      act = torch.as_tensor(act, dtype=torch.float32, device=dev)
-    if act.shape[1] != B or act.shape[2] != A:
-      raise ValueError(f'actions {tuple(act.shape)} != (K, {B}, {A})')
-    if act.stride(-1) != 1:
-      act = act.contiguous()
-    _native.check(lib.bx_env_eval_packed(
-        u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), done_in.data_ptr(), ptr(steps_in),  # pylint: disable=protected-access
-        ptr(rng_in), act.data_ptr(), act.stride(1), act.stride(0), A, ev.data_ptr(),
-        out.data_ptr(), ev.data_ptr(), ptr(rng_out), _stream(dev.index)))
-  return packed.final_state(u, p, state, lay.step_views(out[:lay.block]), rng_out,
+    act = packed.actions_input(actions, B, A, dev)
+    entry, own = 'bx_env_eval_packed', dict(act=act, act_stride=act.stride(1),
+                                            act_step_stride=act.stride(0), act_width=A)
+  rng_out = packed.launch(u, entry, inputs, qbuf, K, out, False, eval_in=ev, eval_out=ev, **own)
+  return packed.final_state(u, inputs[0], state, lay.step_views(out[:lay.block]), rng_out,
                             eval_metrics=unpack_eval_metrics(ev, keys))
 
 

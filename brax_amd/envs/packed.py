@@ -1,5 +1,6 @@
 """What surrounds every packed env launch, once: the output block's layout,
-the inputs a launch reads from a `State`, and the `State` it returns.
+the inputs a launch reads from a `State`, the K-step call itself with its
+arguments by name (`launch`, `refusal`), and the `State` it returns.
 
 `bx_env_step_packed` and the K-step entry points built on it (`rollout`,
 `policy_rollout`, `eval_rollout`, `population_rollout`, `RolloutRunner`) write
@@ -19,6 +20,7 @@ import torch
 from brax_amd import _native
 from brax_amd.base import PackedQP
 from brax_amd.envs.env import State, _f32, _Metrics
+from brax_amd.system import _stream
 
 FIELDS = ('qp', 'obs', 'reward', 'done', 'steps', 'truncation', 'metrics')
 
@@ -129,12 +131,53 @@ def final_state(u, p, state, step, rng_out, info=None, eval_metrics=None):
                metrics=_Metrics(met, keys, extra), info=info)
 
 
-def refusal(u, opts, entry, *args):
+def actions_input(actions, B, A, dev):
+  """Given actions as the (K, B, A) float32 device tensor a launch reads
+  (any strides with a unit last-axis stride)."""
+  act = actions
+  if type(act) is not torch.Tensor or act.dtype != torch.float32 or act.device != dev:
+    act = torch.as_tensor(act, dtype=torch.float32, device=dev)
+  if act.dim() != 3 or act.shape[1] != B or act.shape[2] != A:
+    raise ValueError(f'actions {tuple(act.shape)} != (K, {B}, {A})')
+  return act if act.stride(-1) == 1 else act.contiguous()
+
+
+def output_buffer(name, t, shape, dev):
+  """A caller's buffer `t` for a launch to write: contiguous float32 `shape`
+  on `dev`, or ValueError."""
+  if (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()
+      or t.device != dev):
+    raise ValueError(f'{name} must be contiguous float32 {shape} on {dev}')
+  return t
+
+
+def launch(u, entry, inputs, qbuf, K, out, every_step, **named):
+  """One K-step launch of the entry point `entry` on the caller's stream, its
+  result checked. What the K-step entry points share goes in by name from
+  `inputs` (what `step_inputs` returned), `qbuf` and `out`; `named` are the
+  entry point's own arguments (a tensor stands for its address; the ones left
+  out are NULL or 0). Returns the target envs' streams the launch wrote, or
+  None for a state without them: (K, B) with `every_step`, else (B,)."""
+  p, done_in, steps_in, rng_in = inputs
+  dev, B = u.sys.device, qbuf.shape[0]
+  rng_out = (torch.empty((K, B) if every_step else (B,), dtype=torch.int32, device=dev)
+             if rng_in is not None else None)
+  def addresses(**tensors):
+    return {k: v.data_ptr() if isinstance(v, torch.Tensor) else v for k, v in tensors.items()}
+  _native.check(getattr(_native.lib(), entry)(*_native.args(
+      entry, sys=u.sys._h, env=C.byref(p), n_envs=B, n_steps=K,  # pylint: disable=protected-access
+      stream=_stream(dev.index), **addresses(
+          qp_in=qbuf, done_in=done_in, steps_in=steps_in, rng_in=rng_in, out=out,
+          rng_out=rng_out, **named))))
+  return rng_out
+
+
+def refusal(u, opts, entry, **named):
   """None when the library's entry point `entry` takes the kernel env `u`
-  under `opts` with `args` (those after the params: a zero-step call, so
-  argument checks only and no launch), else the library's reason."""
+  under `opts` with the arguments `named` (a zero-step call, so argument
+  checks only and no launch), else the library's reason."""
   p = u._params(opts, None, None)  # pylint: disable=protected-access
   p.auto_reset = 0
   lib = _native.lib()
-  rc = getattr(lib, entry)(u.sys._h, C.byref(p), *args)  # pylint: disable=protected-access
+  rc = getattr(lib, entry)(*_native.args(entry, sys=u.sys._h, env=C.byref(p), **named))  # pylint: disable=protected-access
   return None if rc == 0 else lib.bx_last_error().decode()

@@ -279,9 +279,7 @@ def _extras(extras, K, B, A, dev):
                         log_prob=torch.empty((K, B), dtype=torch.float32, device=dev))
   for t, shape in ((extras.action, (K, B, A)), (extras.raw_action, (K, B, A)),
                    (extras.log_prob, (K, B))):
-    if (tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev
-        or not t.is_contiguous()):
-      raise ValueError(f'extras must be contiguous float32 {shape} on {dev}')
+    packed.output_buffer('extras', t, shape, dev)
   return extras
 
 
@@ -306,8 +304,7 @@ def fused_supported(env, policy, trajectory: bool = True) -> Optional[str]:
     return f'the policy reads {policy.obs_size} observations, the env writes {u.obs_size}'
   if not trajectory:
     return None
-  return packed.refusal(u, opts, 'bx_env_rollout_policy', 0, 0, None, None, None, None, None,
-                        C.byref(desc), 0, 0, 0, None, None, None, None, None, None)
+  return packed.refusal(u, opts, 'bx_env_rollout_policy', policy=C.byref(desc))
 
 
 def policy_rollout(env, state: State, policy: MLPPolicy, k: int, seed: int = 0, offset: int = 0,
@@ -341,21 +338,17 @@ def policy_rollout(env, state: State, policy: MLPPolicy, k: int, seed: int = 0, 
   qbuf = pack_qp(state.qp, dev)
   B, A, K = qbuf.shape[0], u.action_size, int(k)
   stride = 2 * B * A if step_stride is None else int(step_stride)
-  p, done_in, steps_in, rng_in = packed.step_inputs(u, opts, state, B)
+  inputs = packed.step_inputs(u, opts, state, B)
   obs_in = packed.obs_input(u, state, B)
   lay = packed.layout(u, B)
   out = lay.out_buffer(out, K, dev)
   ex = _extras(extras, K, B, A, dev)
-  rng_out = torch.empty((K, B), dtype=torch.int32, device=dev) if rng_in is not None else None
   desc = policy.descriptor(A)
-  _native.check(_native.lib().bx_env_rollout_policy(
-      u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), obs_in.data_ptr(), done_in.data_ptr(),  # pylint: disable=protected-access
-      None if steps_in is None else steps_in.data_ptr(),
-      None if rng_in is None else rng_in.data_ptr(), C.byref(desc), seed, offset, stride,
-      ex.action.data_ptr(), ex.raw_action.data_ptr(), ex.log_prob.data_ptr(), out.data_ptr(),
-      None if rng_out is None else rng_out.data_ptr(), _stream(dev.index)))
+  rng_out = packed.launch(u, 'bx_env_rollout_policy', inputs, qbuf, K, out, True, obs_in=obs_in,
+                          policy=C.byref(desc), seed=seed, offset=offset, step_stride=stride,
+                          act_out=ex.action, raw_out=ex.raw_action, logp_out=ex.log_prob)
   views = lay.views(out, K)
-  final = packed.final_state(u, p, state, tuple(v[K - 1] for v in views),
+  final = packed.final_state(u, inputs[0], state, tuple(v[K - 1] for v in views),
                              None if rng_out is None else rng_out[K - 1])
   return final, trajectory(u, views, rng_out), ex
 

@@ -250,8 +250,8 @@ def population_supported(env, population, param_stride: Optional[int] = None,
   stride = (0 if pop is None else pop.stride) if param_stride is None else int(param_stride)
   arg = abi.BxPopulation(param_stride=stride,
                          head=abi.HEADS[policy.head] if head is None else abi.HEADS.get(head, -1))
-  return packed.refusal(u, opts, 'bx_env_eval_population', 0, 0, None, None, None, None, None,
-                        C.byref(desc), 0, 0, 0, None, None, None, None, C.byref(arg), None)
+  return packed.refusal(u, opts, 'bx_env_eval_population', policy=C.byref(desc),
+                        pop=C.byref(arg))
 
 
 def population_rollout(env, state: State, population, k: Optional[int] = None, seed: int = 0,
@@ -312,35 +312,32 @@ def population_rollout(env, state: State, population, k: Optional[int] = None, s
   dev = u.sys.device
   qbuf = pack_qp(state.qp, dev)
   A = u.action_size
-  p, done_in, steps_in, rng_in = packed.step_inputs(u, opts, state, B)
+  inputs = packed.step_inputs(u, opts, state, B)
   keys = tuple(u.metric_keys)
   O, M = u.obs_size, len(keys)
   obs_in = packed.obs_input(u, state, B)
   ev, mom = _fresh(carry, keys, B, O, moments, dev)
   for name, buf, shape in (('eval_out', eval_out, (M + 3, B)), ('mom_out', mom_out, (B, 2 * O + 1))):
-    if buf is not None and (tuple(buf.shape) != shape or buf.dtype != torch.float32
-                            or not buf.is_contiguous() or buf.device != dev):
-      raise ValueError(f'{name} must be contiguous float32 {shape} on {dev}')
+    if buf is not None:
+      packed.output_buffer(name, buf, shape, dev)
   if eval_out is not None:
     ev = eval_out.copy_(ev)
   if mom_out is not None and mom is not None:
     mom = mom_out.copy_(mom)
   lay = packed.layout(u, B)
   out = lay.out_buffer(out, 1, dev)
-  rng_out = torch.empty((B,), dtype=torch.int32, device=dev) if rng_in is not None else None
-  ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
   desc = policy.descriptor(A)
   if pop is not None:
     desc.params = pop.rows.data_ptr()
+  mom_ptr = None if mom is None else mom.data_ptr()
   arg = abi.BxPopulation(param_stride=0 if pop is None else pop.stride, head=abi.HEADS[policy.head],
-                         reward_shift=float(reward_shift), mom_in=ptr(mom), mom_out=ptr(mom),
+                         reward_shift=float(reward_shift), mom_in=mom_ptr, mom_out=mom_ptr,
                          flags=abi.POP_NO_STAGE if stage is False else 0)
-  _native.check(_native.lib().bx_env_eval_population(
-      u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), obs_in.data_ptr(), done_in.data_ptr(),  # pylint: disable=protected-access
-      ptr(steps_in), ptr(rng_in), C.byref(desc), int(seed), int(offset), 2 * B * A, ev.data_ptr(),
-      out.data_ptr(), ev.data_ptr(), ptr(rng_out), C.byref(arg), _stream(dev.index)))
+  rng_out = packed.launch(u, 'bx_env_eval_population', inputs, qbuf, K, out, False, obs_in=obs_in,
+                          policy=C.byref(desc), seed=int(seed), offset=int(offset),
+                          step_stride=2 * B * A, eval_in=ev, eval_out=ev, pop=C.byref(arg))
   final = packed.final_state(
-      u, p, state, lay.step_views(out[:lay.block]), rng_out,
+      u, inputs[0], state, lay.step_views(out[:lay.block]), rng_out,
       info={kk: v for kk, v in state.info.items() if kk != 'eval_metrics'})
   return final, _result(ev, mom, keys, O, bool(arg.staged))
 

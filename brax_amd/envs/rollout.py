@@ -91,26 +91,16 @@ def rollout(env, state: State, actions, out: Optional[torch.Tensor] = None
   dev = u.sys.device
   qbuf = pack_qp(state.qp, dev)
   B = qbuf.shape[0]
-  act = actions
-  if type(act) is not torch.Tensor or act.dtype != torch.float32 or act.device != dev:
-    act = torch.as_tensor(act, dtype=torch.float32, device=dev)
-  if act.dim() != 3 or act.shape[1] != B or act.shape[2] != u.action_size:
-    raise ValueError(f'actions {tuple(act.shape)} != (K, {B}, {u.action_size})')
-  if act.stride(-1) != 1:
-    act = act.contiguous()
+  act = packed.actions_input(actions, B, u.action_size, dev)
   K = act.shape[0]
-  p, done_in, steps_in, rng_in = packed.step_inputs(u, opts, state, B)
+  inputs = packed.step_inputs(u, opts, state, B)
   lay = packed.layout(u, B)
   out = lay.out_buffer(out, K, dev)
-  rng_out = torch.empty((K, B), dtype=torch.int32, device=dev) if rng_in is not None else None
-  _native.check(_native.lib().bx_env_rollout_packed(
-      u.sys._h, C.byref(p), B, K, qbuf.data_ptr(), done_in.data_ptr(),  # pylint: disable=protected-access
-      None if steps_in is None else steps_in.data_ptr(),
-      None if rng_in is None else rng_in.data_ptr(), act.data_ptr(), act.stride(1),
-      act.stride(0), act.shape[2], out.data_ptr(),
-      None if rng_out is None else rng_out.data_ptr(), _stream(dev.index)))
+  rng_out = packed.launch(u, 'bx_env_rollout_packed', inputs, qbuf, K, out, True, act=act,
+                          act_stride=act.stride(1), act_step_stride=act.stride(0),
+                          act_width=act.shape[2])
   views = lay.views(out, K)
-  final = packed.final_state(u, p, state, tuple(v[K - 1] for v in views),
+  final = packed.final_state(u, inputs[0], state, tuple(v[K - 1] for v in views),
                              None if rng_out is None else rng_out[K - 1])
   return final, trajectory(u, views, rng_out)
 
@@ -210,9 +200,9 @@ class RolloutRunner:
     self._lib = _native.lib()
     # one-launch draws when the system stages the whole action row (probed
     # with a zero-step call: argument checks only)
-    self.draw = self._lib.bx_env_rollout_random(
-        self._u.sys._h, C.byref(self._p), B, 0, None, None, None, None, 0, 0, 0,  # pylint: disable=protected-access
-        0.0, 1.0, A, None, None, None, None) == 0
+    self.draw = self._lib.bx_env_rollout_random(*_native.args(
+        'bx_env_rollout_random', sys=u.sys._h, env=C.byref(self._p), n_envs=B,  # pylint: disable=protected-access
+        act_width=A, hi=1.0)) == 0
     # the launch's C arguments per buffer parity, built once (run() then
     # passes ctypes objects straight through: the host half of a launch is
     # on the critical path of a short timed region)

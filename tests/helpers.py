@@ -1,5 +1,6 @@
 """Shared test helpers: systems by name and the parity gate."""
 import os
+import re
 
 import numpy as np
 
@@ -338,6 +339,53 @@ def normal_ref(seed, idx, dtype=np.float64):
   out = r * c
   assert out.dtype == np.dtype(dtype)
   return out
+
+
+# ---------------------------------------------------------------------------
+# include/brax_amd.h as data: the one parser of the header (tests/test_abi.py)
+# ---------------------------------------------------------------------------
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                           'include', 'brax_amd.h')
+
+
+def _declarator(text):
+  """'const float* w[BX_MLP_MAX_LAYERS]' -> ('const float*', 'w', 'BX_MLP_MAX_LAYERS')."""
+  ctype, name, dim = re.fullmatch(r'(.*?)(\w+)\s*(?:\[(\w+)\])?', text.strip()).groups()
+  return re.sub(r'\s*\*', '*', ' '.join(ctype.split())), name, dim
+
+
+class Header:
+  """The declarations of the header, comments removed:
+    functions  {name: (return type, [(C type, parameter, array length or None)])}
+    structs    {name: [(C type, field, array length or None)]}, a declaration
+               with several declarators (`bx_field pos, rot;`) one field each
+    constants  {name: int} of the `#define BX_* <integer>` macros and the
+               enumerators
+  all in the header's order."""
+
+  def __init__(self, path=HEADER_PATH):
+    with open(path) as f:
+      self.text = re.sub(r'/\*.*?\*/|//[^\n]*', ' ', f.read(), flags=re.S)
+    self.functions = {}
+    for res, name, params in re.findall(r'^([\w ]+?\*?)\s*\b(bx_\w+)\s*\(([^)]*)\)\s*;', self.text,
+                                        re.M):
+      params = [] if params.strip() == 'void' else params.split(',')
+      self.functions[name] = (' '.join(res.split()), [_declarator(p) for p in params])
+    self.structs = {}
+    for name, body in re.findall(r'typedef\s+struct\s+(bx_\w+)\s*\{(.*?)\}\s*\1\s*;', self.text,
+                                 re.S):
+      fields = self.structs[name] = []
+      for decl in filter(None, (d.strip() for d in body.split(';'))):
+        first, *rest = decl.split(',')
+        ctype, field, dim = _declarator(first)
+        fields.append((ctype, field, dim))
+        for more in rest:  # the header never mixes `T a, *b`
+          assert '*' not in more and not ctype.endswith('*'), decl
+          fields.append((ctype,) + _declarator(more)[1:])
+    self.constants = {n: int(v, 0) for n, v in re.findall(
+        r'^#define\s+(BX_\w+)\s+(-?\w+)\s*$', self.text, re.M) if re.fullmatch(r'-?\d\w*', v)}
+    for body in re.findall(r'\benum\s*\{(.*?)\}', self.text, re.S):
+      self.constants.update({n: int(v, 0) for n, v in re.findall(r'(BX_\w+)\s*=\s*(-?\w+)', body)})
 
 
 class Envelope:

@@ -1,52 +1,12 @@
-"""The evaluation entry points without a GPU: the ABI mirror against the
-header, the `(M + 3, B)` packing, `Evaluator` on the torch-only `fast` env
-(the chained fallback) and the argument checks that need no device."""
-import os
-import re
-
+"""The evaluation entry points without a GPU: the `(M + 3, B)` packing,
+`Evaluator` on the torch-only `fast` env (the chained fallback) and the
+argument checks that need no device (the ABI mirror: tests/test_abi.py)."""
 import numpy as np
 import pytest
 import torch
 
 from brax_amd import _native
 from brax_amd import abi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-_CTYPES = {'int64_t': 'c_long', 'int32_t': 'c_int', 'uint64_t': 'c_ulong'}
-
-
-def _header_args(name):
-  """[(C type, name), ...] of a function declared in include/brax_amd.h."""
-  src = open(os.path.join(ROOT, 'include', 'brax_amd.h')).read()
-  m = re.search(r'^int ' + name + r'\s*\(([^;]*)\);', src, re.M)
-  assert m, name
-  out = []
-  for arg in m.group(1).replace('\n', ' ').split(','):
-    typ, nm = re.match(r'\s*(.*?)(\w+)\s*$', arg).groups()
-    out.append((typ.strip(), nm))
-  return out
-
-
-@pytest.mark.parametrize('name', ['bx_env_eval_policy', 'bx_env_eval_packed'])
-def test_abi_mirrors_the_header(name):
-  hdr = _header_args(name)
-  mine = abi.ARGS[name]
-  assert [n for _, n in hdr] == [n for n, _ in mine]
-  for (ctype, arg), (_, t) in zip(hdr, mine):
-    if ctype == 'const bx_env_params*':
-      assert t._type_ is abi.BxEnvParams, arg
-    elif ctype == 'const bx_policy*':
-      assert t._type_ is abi.BxPolicy, arg
-    elif ctype.endswith('*'):
-      assert t.__name__ == 'c_void_p', arg
-    else:
-      assert t.__name__ == _CTYPES[ctype], (arg, ctype, t)
-  args, res = _native._SIGS[name]  # pylint: disable=protected-access
-  assert args == [t for _, t in mine] and res.__name__ == 'c_int'
-  assert name in _native.EXPORTS
-  # the zero-step probe's arity is the header's
-  assert len(args) == len(hdr)
 
 
 def test_library_exports_the_entry_points():

@@ -2,8 +2,6 @@
 `bx_mlp_backward`, their refusals (host pointers: a launch would fault),
 `fused_supported`'s reasons, and the chained fallbacks' bits."""
 import ctypes as C
-import os
-import re
 
 import pytest
 import torch
@@ -13,26 +11,9 @@ from brax_amd.envs.policy import _ACTIVATIONS
 from brax_amd.training import fused_mlp as fm
 from brax_amd.training import networks
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header_args(src, name):
-  m = re.search(r'^int %s\s*\(([^;]*)\);' % name, src, re.M)
-  assert m, name
-  return [re.match(r'\s*(.*?)(\w+)\s*$', a).group(2) for a in m.group(1).replace('\n', ' ').split(',')]
-
 
 def test_header_abi_and_exports():
-  src = open(os.path.join(ROOT, 'include', 'brax_amd.h')).read()
-  for name in ('bx_mlp_sizes', 'bx_mlp_forward', 'bx_mlp_backward'):
-    assert _header_args(src, name) == [n for n, _ in abi.ARGS[name]]
-    assert name in _native.EXPORTS
-  for struct, mirror in (('bx_mlp', abi.BxMlp), ('bx_mlp_grads', abi.BxMlpGrads)):
-    body = re.search(r'typedef struct %s \{(.*?)\} %s;' % (struct, struct), src, re.S).group(1)
-    assert re.findall(r'(\w+)(?:\[BX_MLP_MAX_LAYERS\])?;', body) == [f for f, _ in mirror._fields_]
-  for name, value in (('LAYERS', abi.MLP_MAX_LAYERS), ('WIDTH', abi.MLP_MAX_WIDTH),
-                      ('IN', abi.MLP_MAX_IN)):
-    assert f'#define BX_MLP_MAX_{name} {value}\n' in src
+  # (names, types, fields and the BX_MLP_MAX_* macros: tests/test_abi.py)
   assert (abi.MLP_MAX_LAYERS, abi.MLP_MAX_WIDTH, abi.MLP_MAX_IN) == (8, 256, 1024)
   # the struct sizes as the library was compiled
   a, b = C.c_int32(0), C.c_int32(0)

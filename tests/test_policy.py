@@ -3,7 +3,6 @@ dict walk, `forward` in float64 against hand-computed values of the head's
 formulas (networks.MLP, NormalTanhDistribution, TanhBijector), and the ABI /
 header declarations of the fused rollout."""
 import math
-import os
 
 import numpy as np
 import pytest
@@ -11,8 +10,6 @@ import torch
 
 from brax_amd import abi
 from brax_amd.envs.policy import MLPPolicy
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _layers(sizes, seed=0):
@@ -158,10 +155,5 @@ def test_chained_rollout_on_the_torch_only_env():
 
 
 def test_abi_version_and_header():
+  # (the entry points, bx_policy and BX_POLICY_MAX_* against the header: tests/test_abi.py)
   assert abi.ABI_VERSION == 14
-  src = open(os.path.join(ROOT, 'include', 'brax_amd.h')).read()
-  assert '#define BX_ABI_VERSION 14' in src
-  assert 'int bx_env_rollout_policy(' in src and 'int bx_normal_slabs(' in src
-  assert 'typedef struct bx_policy' in src
-  assert f'#define BX_POLICY_MAX_LAYERS {abi.POLICY_MAX_LAYERS}' in src
-  assert f'#define BX_POLICY_MAX_WIDTH {abi.POLICY_MAX_WIDTH}' in src

@@ -8,7 +8,6 @@ import ctypes as C
 import functools
 import inspect
 import os
-import re
 
 import pytest
 import torch
@@ -24,23 +23,11 @@ P = 0x7f0000001000  # a "device pointer": non-null, 4 KiB aligned
 T31 = 1 << 31
 
 
-def _header_args(src, name):
-  m = re.search(r'^int %s\s*\(([^;]*)\);' % name, src, re.M)
-  assert m, name
-  return [re.match(r'\s*(.*?)(\w+)\s*$', a).group(2) for a in m.group(1).replace('\n', ' ').split(',')]
-
-
 def test_header_abi_and_exports():
-  src = open(os.path.join(ROOT, 'include', 'brax_amd.h')).read()
-  for name in NAMES:
-    assert _header_args(src, name) == [n for n, _ in abi.ARGS[name]]
-    assert name in _native.EXPORTS
-    assert getattr(_native.lib(), name).argtypes == [t for _, t in abi.ARGS[name]]
-  assert '#define BX_SAC_MAX_CRITICS 4\n' in src and abi.SAC_MAX_CRITICS == 4
-  assert '#define BX_SAC_MAX_JOBS 3\n' in src and abi.SAC_MAX_JOBS == 3
+  # (names, types and the macros against the header: tests/test_abi.py)
+  assert abi.SAC_MAX_CRITICS == 4 and abi.SAC_MAX_JOBS == 3
   # additive: the version stays
   assert abi.ABI_VERSION == 14 and _native.lib().bx_abi_version() == 14
-  assert '#define BX_ABI_VERSION 14\n' in src
 
 
 def wsb(n=1 << 20):
