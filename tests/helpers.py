@@ -116,8 +116,45 @@ def golden_reset_qp(name, o, T):
 MID = ['mid_pusher', 'mid_halfcheetah', 'mid_hopper', 'mid_walker2d', 'mid_humanoidstandup']
 # Grasp's env step moves the palm and maps the action before System.step
 # (grasp.py:73-87), so its env-layer fixture's actions are not System.step's:
-# it serves the env gate only
+# the env gate takes the file as it is, the system gate takes what
+# oracle/mid_states.py `pre_step` makes of its states and actions (the action
+# map and the palm move in float64 on the host). 16 envs, not 8
 MID_ENV = ['mid_grasp']
+
+# the target envs' steps teleport a hit target to a random spot AFTER the
+# observation, the reward and the metrics are taken (ur5e.py:83-89,
+# fetch.py:90-96, grasp.py:130-136): only that body's pos is replaced, its
+# rot / vel / ang stay the physics'. The reference draws the spot from a JAX
+# key, the HIP env from its own counter stream, and the C oracle does not
+# restate it (parity-unpinned), so on a sample whose recorded
+# `hits` metric is 1 the recorded next state's target pos is compared with
+# nothing: env kind -> the body
+TELEPORTS = {'ur5e': 'Target', 'fetch': 'Target', 'grasp': 'Target'}
+
+
+def teleported(name, T):
+  """Of an env-layer golden `T` of the golden name `name`: (the teleported
+  body's index, (steps, B) bool: the recorded `hits` metric is 1, the target
+  of that sample's step was teleported), or (None, None) for an env kind
+  whose step teleports nothing."""
+  body = TELEPORTS.get(env_kind(name))
+  if body is None:
+    return None, None
+  hits = T['metrics'][..., [str(k) for k in T['metric_keys']].index('hits')]
+  assert np.isin(hits, (0.0, 1.0)).all()
+  return compiled(name)[3]['body_index'][body], hits == 1.0
+
+
+def without_teleported(qp, body, hit):
+  """A copy of the states `qp` (B, N, 13) with the pos of `body` taken out
+  (zeroed: it then adds nothing to a normwise error or its scale) on the
+  envs `hit` (B,) bool; the body's rot / vel / ang and every other sample
+  stay. `body` None: `qp` itself."""
+  if body is None:
+    return qp
+  qp = np.array(qp, copy=True)
+  qp[hit, body, 0:3] = 0
+  return qp
 
 
 def env_golden(name):

@@ -24,10 +24,10 @@ import torch
 
 from tests.conftest import golden
 from tests.margins import record_exact, record_margin
-from tests.helpers import (CAPSULES, MID, N_PERTURB, NEAR_TOL, WIDE, Envelope, NN_MASKED,
+from tests.helpers import (CAPSULES, MID, MID_ENV, N_PERTURB, NEAR_TOL, WIDE, Envelope, NN_MASKED,
                            SHORT_SCENES, ENVTRAJ_KERNEL, POINTS, QP_FIELDS, ROBOTS, SPRING_ENVS, SPRING_ROBOTS, XCOL, XY_ENVS, compiled, env_golden, env_kind,
                            golden_reset_qp, normwise, obs_flags, prep_oracle, reset_bodies,
-                           sys_golden)
+                           sys_golden, teleported, without_teleported)
 
 pytestmark = pytest.mark.gpu
 
@@ -201,8 +201,21 @@ def _pattern_gate(pen, ref_pen, o_pen, e_all, rows, where):
 
 
 @pytest.mark.parametrize('name', ENV_TRAJ + SYS_TRAJ + [r + ':generic' for r in ROBOTS] + MID +
-                         ['mid_pusher:generic', 'mid_hopper:generic', 'mid_walker2d:generic'])
+                         MID_ENV + ['mid_pusher:generic', 'mid_hopper:generic',
+                                    'mid_walker2d:generic', 'mid_grasp:generic'])
 def test_system_step_vs_golden(dev, oracle_lib, name):
+  """One System.step from every recorded state against the reference: the
+  next state, Info.contact, the contact rows' pos / normal / penetration.
+
+  The fixtures of MID_ENV (`mid_grasp`) record an env whose step changes the
+  state and the action before its System.step, so their System.step inputs
+  are oracle/mid_states.py `pre_step` of the recorded ones (float64, on the
+  host); the kernel, the envelope and the float64 oracle get the same arrays,
+  and the float64 oracle's step of them is asserted to be the recorded one
+  (1e-9), so a wrong input cannot pass as a kernel error or hide one. The
+  recorded next state is the env's: on the samples whose target the env
+  teleported after the step, that body's pos is taken out of the HIP output,
+  the reference and every realisation alike (tests/helpers.py TELEPORTS)."""
   name, _, variant = name.partition(':')
   sys_ = _system(name, dev)
   if variant == 'generic':
@@ -210,6 +223,19 @@ def test_system_step_vs_golden(dev, oracle_lib, name):
     _native.check(_native.lib().bx_system_set_single(sys_._h, 0))
   T = golden(sys_golden(name))
   compared = 0
+  pre = None
+  tbody, thit = None, None
+  if name in MID_ENV:
+    from oracle import mid_states
+    meta = compiled(name)[3]
+    o64 = prep_oracle(oracle_lib.Oracle(*compiled(name)[1:3], np.float64, safe_guard=False), name)
+    tbody, thit = teleported(name, T)
+
+    def pre(qp, act):
+      # the system reads its own action_size columns; the palm's three past
+      # them are spent by the move
+      q, a = mid_states.pre_step(env_kind(name), meta, qp, act)
+      return q, np.ascontiguousarray(a[:, :sys_.action_size])
   # 32 perturbed copies per build (N_PERTURB): the envelope is a max over samples, and 3 understate
   # it for small batches and for sums over discontinuous gates (legacy_spring
   # Info.contact sums an impulse pass per substep through `penetration > 0`,
@@ -218,12 +244,20 @@ def test_system_step_vs_golden(dev, oracle_lib, name):
   # scenes such as the height map likewise)
   env32 = Envelope(oracle_lib, name)
   for t in range(T['action'].shape[0]):
-    qp_in = _to_qp(T['qp'][t], dev)
-    act = torch.as_tensor(T['action'][t], dtype=torch.float32, device=dev)
+    q_in, a_in = (T['qp'][t], T['action'][t]) if pre is None else pre(T['qp'][t], T['action'][t])
+    hit = None if thit is None else thit[t]
+    qp_in = _to_qp(q_in, dev)
+    act = torch.as_tensor(a_in, dtype=torch.float32, device=dev)
     out, info = sys_.step(qp_in, act)
-    got = _qp_np(out)
-    ref = T['qp'][t + 1]
-    outs = env32.system(T['qp'][t], T['action'][t])
+    got = without_teleported(_qp_np(out), tbody, hit)
+    ref = without_teleported(T['qp'][t + 1], tbody, hit)
+    outs = env32.system(q_in, a_in)
+    outs = [(without_teleported(o[0], tbody, hit), o[1]) for o in outs]
+    if pre is not None:
+      r64, i64 = o64.system_step(q_in, a_in)
+      assert normwise(without_teleported(r64, tbody, hit), ref).max() <= 1e-9
+      assert normwise(i64['contact'], T['info_contact'][t]).max() <= 1e-9
+      assert normwise(i64['contact_penetration'], T['contact_penetration'][t]).max() <= 1e-9
     e_all = np.zeros(got.shape[0])  # the largest E32 per env over the gated fields
     for f, sl in QP_FIELDS.items():
       e32 = _env_err([o[0][..., sl] for o in outs], ref[..., sl])
@@ -267,7 +301,8 @@ def test_system_step_vs_golden(dev, oracle_lib, name):
 
 
 @pytest.mark.parametrize('name', ENV_TRAJ + XY_ENVS + ENVTRAJ_KERNEL +
-                         ['ant:nojb', 'halfcheetah:nojb'] + MID + ['mid_halfcheetah:nojb'])
+                         ['ant:nojb', 'halfcheetah:nojb'] + MID + MID_ENV +
+                         ['mid_halfcheetah:nojb'])
 def test_env_step_vs_golden(dev, oracle_lib, name, monkeypatch):
   """One env step from every recorded state against the reference: obs, reward,
   done, metrics. On the mid-episode fixtures (`mid_*`: contact rows at work)
@@ -279,12 +314,28 @@ def test_env_step_vs_golden(dev, oracle_lib, name, monkeypatch):
   zero margin flips in Brax's own fp32), and that gate asserts that it
   compared at least one penetrating row.
 
-  `mid_grasp` (tests/helpers.py MID_ENV) is not in this list yet: its obs gate
-  passed, but on one ill-conditioned env the next state's pos was 9.09e-1
-  (normwise) from the nearest fp32 realisation against a bound of 1e-3
-  (`qp_pos:illcond_nearest`, ratio 909), and the cause (the kernel's contact
-  halves, or a body the Grasp env program places itself) is not found. The
-  fixture and its census stay."""
+  The target envs teleport a hit target after the observation is taken
+  (tests/helpers.py TELEPORTS): the reference draws the spot from its JAX key,
+  the kernel from the env's counter stream, the oracle leaves the target
+  where the physics did. On the (step, env) samples whose recorded `hits` is
+  1 (`mid_grasp`: step 0, envs 4 and 8) the target's pos is therefore taken
+  out of the `qp_pos` gate, in the kernel's output, the reference and every
+  realisation alike; its rot / vel / ang and every other sample stay gated.
+  There the kernel's spot is held to the teleport's contract instead
+  (test_gpu_envs.py test_target_teleport_stream): x-y radius within
+  [radius, radius + distance], Grasp's height in [0, 8), and every env's
+  stream advanced by one. `hits` itself is asserted exactly: every fp32
+  realisation agrees with the reference on it (tests/test_golden_coverage.py
+  pins that on the CPU).
+
+  Before this mask `mid_grasp` was left out of the list: `qp_pos` was 9.09e-1
+  from the nearest fp32 realisation on one env (`qp_pos:illcond_nearest`
+  against 1e-3). That was no rounding: the 66 realisations agree with each
+  other to 1.7e-7 and sit 0.63 and 1.0 (normwise) from the reference's
+  teleported target on envs 4 and 8, so the gate took a gap between the
+  oracle's model and the reference's for an ill-conditioned sample and then
+  measured the kernel's own random spot against the oracle's unmoved target.
+  tests/test_golden_coverage.py now lists every such gap explicitly."""
   name, _, variant = name.partition(':')
   if variant == 'nojb':
     # the all-kinds kernel the Ant / HalfCheetah kinds fall back to when their
@@ -297,10 +348,15 @@ def test_env_step_vs_golden(dev, oracle_lib, name, monkeypatch):
   O, M = T['obs'].shape[-1], T['metrics'].shape[-1]
   assert env.observation_size == O
   from brax_amd.envs.env import State
+  tbody, thit = teleported(name, T)
   for t in range(T['action'].shape[0]):
     B = T['qp'].shape[1]
+    info = {}
+    if getattr(env, 'needs_rng', False):  # the target envs' streams, as a reset starts them
+      from brax_amd.envs import tasks
+      info['rng'] = tasks.rng_streams(0, 0, B, dev)
     st = State(qp=_to_qp(T['qp'][t], dev), obs=None,
-               reward=torch.zeros(B, device=dev), done=torch.zeros(B, device=dev))
+               reward=torch.zeros(B, device=dev), done=torch.zeros(B, device=dev), info=info)
     act = torch.as_tensor(T['action'][t], dtype=torch.float32, device=dev)
     nst = env.step(st, act)
     outs = env32.env(env_kind(name), T['qp'][t], T['action'][t], O, M, fl, env.coef)
@@ -313,10 +369,30 @@ def test_env_step_vs_golden(dev, oracle_lib, name, monkeypatch):
       # the mid-episode fixtures: the env kernels write no Info (no
       # penetrations to compare patterns on), so the whole next state is gated
       # as well: a contact row the kernel skipped moves its bodies
-      got = _qp_np(nst.qp)
+      hit = None if thit is None else thit[t]
+      raw = _qp_np(nst.qp)
+      got = without_teleported(raw, tbody, hit)
+      ref = without_teleported(T['qp'][t + 1], tbody, hit)
+      qps = [without_teleported(o[0], tbody, hit) for o in outs]
       for f, sl in QP_FIELDS.items():
-        _gate(got[..., sl], T['qp'][t + 1][..., sl],
-              _env_err([o[0][..., sl] for o in outs], T['qp'][t + 1][..., sl]), 'qp_' + f)
+        _gate(got[..., sl], ref[..., sl], _env_err([q[..., sl] for q in qps], ref[..., sl]),
+              'qp_' + f)
+      if tbody is not None:
+        # `hits` decides the teleport: exactly the reference's; a hit target's
+        # spot: the teleport's contract, never the reference's draw
+        k = list(env.metric_keys).index('hits')
+        assert np.array_equal(nst.metrics['hits'].cpu().numpy(), T['metrics'][t][:, k])
+        assert torch.equal(nst.info['rng'], info['rng'] + 1)
+        c = env.coef
+        radius, distance, height = ((c[4], c[5], None) if env_kind(name) == 'grasp'
+                                    else (c[2], c[3], c[4]))
+        spot = raw[hit, tbody, 0:3]
+        r = np.linalg.norm(spot[:, :2], axis=-1)
+        assert (r >= radius - 1e-4).all() and (r <= radius + distance + 1e-4).all(), r
+        if height is None:
+          assert (spot[:, 2] >= 0).all() and (spot[:, 2] < 8).all(), spot[:, 2]
+        else:
+          np.testing.assert_allclose(spot[:, 2], height, atol=1e-6)
     if env.metric_keys:
       met = np.stack([nst.metrics[k].cpu().numpy() for k in env.metric_keys], -1)
       _gate(met, T['metrics'][t], _env_err([o[4] for o in outs], T['metrics'][t]), 'metrics')

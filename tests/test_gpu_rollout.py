@@ -253,15 +253,19 @@ def target_rows_penetrate(oracle_lib, name, T, st0, tr, acts):
   """(rows, envs per row): the fixture's target rows that penetrate at some
   step of the GPU trajectory `tr`, and on how many envs each does: the
   float64 oracle's Info on the states the steps started from (the start
-  state, then the kernel's own recorded states)."""
+  state, then the kernel's own recorded states), each as the env hands it to
+  System.step (oracle/mid_states.py `pre_step`: Grasp's palm move and action
+  map)."""
+  from oracle import mid_states
   from tests.helpers import compiled
-  _, d, rd, _ = compiled(name)
+  _, d, rd, meta = compiled(name)
   o64 = oracle_lib.Oracle(d, rd, np.float64)
   q0 = torch.cat([st0.qp.pos, st0.qp.rot, st0.qp.vel, st0.qp.ang], -1)
   ins = [q0] + [tr.qp[t][..., :13] for t in range(acts.shape[0] - 1)]
   hit = 0
   for q, a in zip(ins, acts):
-    pen = o64.system_step(q.cpu().numpy(), a.cpu().numpy())[1]['contact_penetration']
+    q, a = mid_states.pre_step(name, meta, q.cpu().numpy(), a.cpu().numpy())
+    pen = o64.system_step(q, a)[1]['contact_penetration']
     hit = hit | (pen[:, T['row_target']] > 0)
   return set(T['row_target'][hit.any(0)].tolist()), hit.sum(0)[hit.any(0)].tolist()
 
@@ -272,11 +276,13 @@ def fixture_rows(T):
   return set(tr[(T['contact_penetration'][..., tr] > 0).any((0, 1))].tolist())
 
 
-@pytest.mark.parametrize('name', ['pusher', 'halfcheetah'])
+@pytest.mark.parametrize('name', ['pusher', 'halfcheetah', 'grasp'])
 def test_rollout_from_contact_states(dev, oracle_lib, name):
   """The K-step kernel from states whose contact rows are at work (the
   mid-episode fixtures: Pusher's arm - object capsule pairs, HalfCheetah's
-  foot - foot pair), not from `reset`: every field bit-identical to chained
+  foot - foot pair, Grasp's object - palm and object - fingertip pairs, with
+  two hit targets teleported inside the trajectory), not from `reset`: every
+  field bit-identical to chained
   `env.step`, and the target rows penetrate inside the trajectory."""
   env, st0, acts, T = contact_start(name, dev)
   tr = _check(env, st0, acts)
