@@ -22,52 +22,17 @@ Prints one JSON line per measurement.
 
     python tools/es_bench.py [--runs 7] [--calls 50] [--epochs 3] [--learn]
 """
-import argparse
-import json
-import os
-import statistics
-import sys
 import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-from brax_amd import envs  # noqa: E402
-from brax_amd.envs import wrappers  # noqa: E402
-from brax_amd.envs.policy import MLPPolicy  # noqa: E402
-from brax_amd.envs.population import (PolicyPopulation, population_rollout,  # noqa: E402
-                                      population_supported)
-from brax_amd.training import ars, es  # noqa: E402
-
-ANT_OBS, ANT_ACT = 87, 8
-
-
-def spread(xs, scale=1.0, digits=2):
-  return {'median': round(statistics.median(xs) * scale, digits),
-          'min': round(min(xs) * scale, digits), 'max': round(max(xs) * scale, digits)}
-
-
-def region(fn, calls, dev):
-  torch.cuda.synchronize(dev)
-  t = time.perf_counter()
-  for _ in range(calls):
-    fn()
-  torch.cuda.synchronize(dev)
-  return (time.perf_counter() - t) / calls
-
-
-def alternate(forms, runs, calls, dev):
-  times = {k: [] for k in forms}
-  for fn in forms.values():
-    region(fn, max(calls // 4, 1), dev)  # warm-up
-  for _ in range(runs):
-    for k, fn in forms.items():
-      times[k].append(region(fn, calls, dev))
-  return times
+from measure import ANT_ACT, ANT_OBS, alternate, emit, spread, start, timed, tool_args
 
 
 def bench_kernels(dev, agent, P, runs, calls):
+  from brax_amd.envs.policy import MLPPolicy  # pylint: disable=import-outside-toplevel
+  from brax_amd.envs.population import PolicyPopulation  # pylint: disable=import-outside-toplevel
+  from brax_amd.training import ars, es  # pylint: disable=import-outside-toplevel
   if agent == 'es':
     layers = es.make_es_networks(ANT_OBS, ANT_ACT, seed=0, device=dev)
     policy = MLPPolicy([(w.detach(), b.detach()) for w, b in layers], activation='relu', device=dev)
@@ -93,28 +58,32 @@ def bench_kernels(dev, agent, P, runs, calls):
           'runs': runs, 'calls_per_region': calls}
   t = alternate({'fused': lambda: pop.perturb_(sigma, 1, 0, frozen=frozen, fused=True),
                  'chained': lambda: ref.perturb_(sigma, 1, 0, frozen=frozen, fused=False)},
-                runs, calls, dev)
+                runs, calls, dev, warmup_calls=max(calls // 4, 1))
   res = {'measure': 'perturb', **head, 'bit_identical': same,
          # what the fused form moves: theta once per direction (cached) and the rows
          'fused_bytes_written': 2 * P * n * 4}
   res.update({k: spread(v, 1e6) for k, v in t.items()})
   res['chained_over_fused'] = round(res['chained']['median'] / res['fused']['median'], 2)
   res['fused_store_GB_per_s'] = round(res['fused_bytes_written'] / res['fused']['median'] / 1e3, 1)
-  print(json.dumps(res), flush=True)
+  emit(res)
   t = alternate({'fused': lambda: pop.weighted_noise_sum(w, 1, 0, frozen=frozen, fused=True,
                                                          workspace=ws),
                  'chained': lambda: pop.weighted_noise_sum(w, 1, 0, frozen=frozen, fused=False)},
-                runs, calls, dev)
+                runs, calls, dev, warmup_calls=max(calls // 4, 1))
   res = {'measure': 'weighted_noise_sum', **head,
          'nonzero_weights': int((w != 0).sum()),
          'max_abs_difference': float((a.double() - b.double()).abs().max()),
          'max_abs_value': float(b.abs().max())}
   res.update({k: spread(v, 1e6) for k, v in t.items()})
   res['chained_over_fused'] = round(res['chained']['median'] / res['fused']['median'], 2)
-  print(json.dumps(res), flush=True)
+  emit(res)
 
 
 def bench_epoch(dev, P, epochs):
+  from brax_amd import envs  # pylint: disable=import-outside-toplevel
+  from brax_amd.envs import wrappers  # pylint: disable=import-outside-toplevel
+  from brax_amd.envs.population import population_rollout, population_supported  # pylint: disable=import-outside-toplevel
+  from brax_amd.training import es  # pylint: disable=import-outside-toplevel
   env = envs.create('ant', episode_length=1000, batch_size=2 * P, device=dev)
   L = es.Learner(env, population_size=P, episode_length=1000,
                  fitness_shaping=es.FitnessShaping.CENTERED_RANK, normalize_observations=True,
@@ -124,32 +93,24 @@ def bench_epoch(dev, P, epochs):
 
   def phases(fused):
     out = {}
-
-    def timed(name, fn):
-      torch.cuda.synchronize(dev)
-      t = time.perf_counter()
-      r = fn()
-      torch.cuda.synchronize(dev)
-      out[name] = time.perf_counter() - t
-      return r
     key[0], reset_key = wrappers.split_key(key[0])
-    state = timed('reset', lambda: env.reset(reset_key))
-    timed('perturb', lambda: L.population.perturb_(L.perturbation_std, L.param_seed, L.param_offset,
-                                                   fused=fused))
-    _, res = timed('episodes', lambda: population_rollout(env, state, L.population, 1000,
-                                                          seed=L.action_seed,
-                                                          offset=L.action_offset))
-    timed('normaliser', lambda: L.normalizer.update_from_moments(res))
-    w = timed('weights', lambda: es.es_weights(res.scores, L.fitness_shaping, L.center_fitness))
-    delta = timed('delta', lambda: L.population.weighted_noise_sum(
+    out['reset'], state = timed(lambda: env.reset(reset_key), dev)
+    out['perturb'], _ = timed(lambda: L.population.perturb_(
+        L.perturbation_std, L.param_seed, L.param_offset, fused=fused), dev)
+    out['episodes'], (_, res) = timed(lambda: population_rollout(
+        env, state, L.population, 1000, seed=L.action_seed, offset=L.action_offset), dev)
+    out['normaliser'], _ = timed(lambda: L.normalizer.update_from_moments(res), dev)
+    out['weights'], w = timed(
+        lambda: es.es_weights(res.scores, L.fitness_shaping, L.center_fitness), dev)
+    out['delta'], delta = timed(lambda: L.population.weighted_noise_sum(
         w, L.param_seed, L.param_offset, fused=fused,
-        workspace=L._workspace if fused is not False else None))  # pylint: disable=protected-access
+        workspace=L._workspace if fused is not False else None), dev)  # pylint: disable=protected-access
 
     def update():
       L.theta.grad = L.gradient(delta)
       L.optimizer.step()
       L.publish()
-    timed('update', update)
+    out['update'], _ = timed(update, dev)
     L.param_offset += 2 * P * L.population.n_params
     L.action_offset += 1000 * 2 * 2 * P * env.action_size
     out['env_steps'] = int(res.obs_count.double().sum().item())
@@ -172,16 +133,17 @@ def bench_epoch(dev, P, epochs):
   total = lambda recs: [sum(v for k, v in r.items() if k != 'env_steps') for r in recs]  # noqa: E731
   res['epoch_fused'] = spread(total(rec[None]), 1e3)
   res['epoch_chained'] = spread(total(rec[False]), 1e3)
-  print(json.dumps(res), flush=True)
+  emit(res)
 
 
 def learn(dev, agent, num_timesteps, num_evals):
+  from brax_amd.training import ars, es  # pylint: disable=import-outside-toplevel
   curve = []
 
   def progress(step, m):
     curve.append({'env_steps': step, 'eval/episode_reward': round(float(m['eval/episode_reward']), 2),
                   'eval/avg_episode_length': round(float(m['eval/avg_episode_length']), 1)})
-    print(json.dumps({'measure': 'learn_progress', 'agent': agent, **curve[-1]}), flush=True)
+    emit({'measure': 'learn_progress', 'agent': agent, **curve[-1]})
   t = time.perf_counter()
   if agent == 'ars':
     cfg = dict(number_of_directions=60, top_directions=20, step_size=0.015,
@@ -197,25 +159,19 @@ def learn(dev, agent, num_timesteps, num_evals):
                              progress_fn=progress,
                              fitness_shaping=es.FitnessShaping.CENTERED_RANK, **cfg)
     cfg['fitness_shaping'] = 'centered_rank'
-  print(json.dumps({'measure': 'learn', 'agent': agent, 'env': 'inverted_pendulum', **cfg,
-                    'num_timesteps': num_timesteps, 'wall_s': round(time.perf_counter() - t, 1),
-                    'training/sps': round(float(metrics['training/sps'])), 'curve': curve}),
-        flush=True)
+  emit({'measure': 'learn', 'agent': agent, 'env': 'inverted_pendulum', **cfg,
+        'num_timesteps': num_timesteps, 'wall_s': round(time.perf_counter() - t, 1),
+        'training/sps': round(float(metrics['training/sps'])), 'curve': curve})
 
 
 def main():
-  ap = argparse.ArgumentParser()
-  ap.add_argument('--runs', type=int, default=7)
-  ap.add_argument('--calls', type=int, default=50)
+  ap = tool_args(__doc__, runs=7, calls=50)
   ap.add_argument('--epochs', type=int, default=3)
   ap.add_argument('--learn', action='store_true')
   ap.add_argument('--learn-timesteps', type=int, default=2_000_000)
   ap.add_argument('--learn-evals', type=int, default=6)
   ap.add_argument('--skip-epoch', action='store_true')
-  a = ap.parse_args()
-  if not torch.cuda.is_available():
-    sys.exit('es_bench needs a GPU: a CPU run gives no time')
-  dev = torch.device('cuda', 0)
+  a, dev = start('es_bench', ap)
   bench_kernels(dev, 'es', 4096, a.runs, a.calls)
   bench_kernels(dev, 'ars', 60, a.runs, a.calls)
   if not a.skip_epoch:

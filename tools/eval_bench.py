@@ -20,42 +20,28 @@ batch).
 
     python tools/eval_bench.py [--envs 128 4096] [--runs 5]
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-from brax_amd import envs  # noqa: E402
-from brax_amd.envs.evaluator import Evaluator, eval_rollout  # noqa: E402
-from brax_amd.envs.policy import policy_rollout  # noqa: E402
-from tools.policy_rollout_bench import ppo_policy  # noqa: E402
+from measure import emit, regions, spread, start, tool_args
+from policy_rollout_bench import ppo_policy
 
 EP = 1000
 
 
-def timed(run, runs, warmup):
-  """(median, min, max) seconds of `runs` calls and the peak bytes allocated."""
+def evaluation(run, runs, warmup, dev):
+  """One loop's entry: us per env step over `runs` whole evaluations after the
+  warm-up, and the peak allocation of the timed runs alone."""
   for _ in range(warmup):
     run()
-  torch.cuda.synchronize()
+  torch.cuda.synchronize(dev)
   torch.cuda.reset_peak_memory_stats()
-  out = []
-  for _ in range(runs):
-    t0 = time.perf_counter()
-    run()
-    torch.cuda.synchronize()
-    out.append(time.perf_counter() - t0)
-  return statistics.median(out), min(out), max(out), torch.cuda.max_memory_allocated()
+  entry = spread(regions(run, runs, 1, dev), 1e6 / EP, 3)
+  entry['peak_MiB'] = round(torch.cuda.max_memory_allocated() / 2**20, 1)
+  return entry
 
 
-def chunked(env, st0, policy, K):
+def chunked(policy_rollout, env, st0, policy, K):
   """(b): the trajectory kernel in K-step chunks, EvalWrapper's sums per chunk."""
   B = st0.obs.shape[0]
   dev = st0.obs.device
@@ -79,13 +65,14 @@ def chunked(env, st0, policy, K):
 
 
 def main():
-  ap = argparse.ArgumentParser()
+  ap = tool_args(__doc__, runs=5)
   ap.add_argument('--envs', type=int, nargs='+', default=[128, 4096])
-  ap.add_argument('--runs', type=int, default=5)
   ap.add_argument('--warmup', type=int, default=1)
   ap.add_argument('--k', type=int, default=50)
-  a = ap.parse_args()
-  dev = torch.device('cuda', 0)
+  a, dev = start('eval_bench', ap)
+  from brax_amd import envs  # pylint: disable=import-outside-toplevel
+  from brax_amd.envs.evaluator import Evaluator, eval_rollout  # pylint: disable=import-outside-toplevel
+  from brax_amd.envs.policy import policy_rollout  # pylint: disable=import-outside-toplevel
   for B in a.envs:
     eval_env = envs.create('ant', batch_size=B, episode_length=EP, auto_reset=True,
                            eval_metrics=True, device=dev)
@@ -95,19 +82,17 @@ def main():
            'unit': 'us per env step (whole batch)'}
 
     def record(name, run):
-      med, lo, hi, peak = timed(run, a.runs, a.warmup)
-      res[name] = {'median': round(med / EP * 1e6, 3), 'min': round(lo / EP * 1e6, 3),
-                   'max': round(hi / EP * 1e6, 3), 'peak_MiB': round(peak / 2**20, 1)}
+      res[name] = evaluation(run, a.runs, a.warmup, dev)
 
     ev = Evaluator(eval_env, policy, num_eval_envs=B, episode_length=EP, fused=True)
     record('a_run_evaluation', ev.run_evaluation)
     record('a_eval_rollout', lambda: eval_rollout(eval_env, st0, k=EP, policy=policy, fused=True))
-    record('b_chunked_trajectory', lambda: chunked(eval_env.env, st0, policy, a.k))
+    record('b_chunked_trajectory', lambda: chunked(policy_rollout, eval_env.env, st0, policy, a.k))
     record('c_chained_eval_env', lambda: policy_rollout(eval_env, st0, policy, EP))
     rb = res['b_chunked_trajectory']['median']
     for k in ('a_run_evaluation', 'a_eval_rollout', 'c_chained_eval_env'):
       res[k]['over_b'] = round(res[k]['median'] / rb, 3)
-    print(json.dumps(res), flush=True)
+    emit(res)
 
 
 if __name__ == '__main__':

@@ -14,26 +14,16 @@ Prints one JSON line (microseconds per env step of the whole batch).
 
     python tools/policy_rollout_bench.py [--envs 4096] [--k 50]
 """
-import argparse
-import json
 import math
-import os
-import statistics
-import sys
-import time
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-from brax_amd import envs  # noqa: E402
-from brax_amd.base import PackedQP, packed_buffer  # noqa: E402
-from brax_amd.envs.policy import MLPPolicy, PolicyExtras, policy_rollout  # noqa: E402
-from brax_amd.envs.rollout import RolloutRunner, chain_options  # noqa: E402
+from measure import emit, regions, spread, start, tool_args
 
 
 def ppo_policy(env, dev, deterministic=False, seed=0):
+  from brax_amd.envs.policy import MLPPolicy  # pylint: disable=import-outside-toplevel
   g = torch.Generator(device='cpu').manual_seed(seed)
   sizes = (env.observation_size, 32, 32, 32, 32, 2 * env.action_size)
   layers = []
@@ -46,30 +36,18 @@ def ppo_policy(env, dev, deterministic=False, seed=0):
                    device=dev)
 
 
-def timed(chunk, regions, reps, warmup):
-  """Median seconds per chunk over `regions` regions of `reps` chunks."""
-  for _ in range(warmup):
-    chunk()
-  torch.cuda.synchronize()
-  out = []
-  for _ in range(regions):
-    t0 = time.perf_counter()
-    for _ in range(reps):
-      chunk()
-    torch.cuda.synchronize()
-    out.append((time.perf_counter() - t0) / reps)
-  return statistics.median(out), min(out), max(out)
-
-
 def main():
-  ap = argparse.ArgumentParser()
+  ap = tool_args(__doc__)
   ap.add_argument('--envs', type=int, default=4096)
   ap.add_argument('--k', type=int, default=50)
   ap.add_argument('--regions', type=int, default=7)
   ap.add_argument('--reps', type=int, default=10)
   ap.add_argument('--warmup', type=int, default=3)
-  a = ap.parse_args()
-  dev = torch.device('cuda', 0)
+  a, dev = start('policy_rollout_bench', ap)
+  from brax_amd import envs  # pylint: disable=import-outside-toplevel
+  from brax_amd.base import PackedQP, packed_buffer  # pylint: disable=import-outside-toplevel
+  from brax_amd.envs.policy import PolicyExtras, policy_rollout  # pylint: disable=import-outside-toplevel
+  from brax_amd.envs.rollout import RolloutRunner, chain_options  # pylint: disable=import-outside-toplevel
   B, K = a.envs, a.k
   env = envs.create('ant', batch_size=B, episode_length=1000, auto_reset=True, device=dev)
   A = env.action_size
@@ -77,9 +55,7 @@ def main():
          'unit': 'us per env step (whole batch)'}
 
   def record(name, chunk):
-    med, lo, hi = timed(chunk, a.regions, a.reps, a.warmup)
-    res[name] = {'median': round(med / K * 1e6, 3), 'min': round(lo / K * 1e6, 3),
-                 'max': round(hi / K * 1e6, 3)}
+    res[name] = spread(regions(chunk, a.regions, a.reps, dev, a.warmup), 1e6 / K, 3)
 
   # (a) open-loop, in-kernel uniform draws
   runner = RolloutRunner(env, env.reset(np.array([0, 1], np.uint32)), K, seed=1)
@@ -151,7 +127,7 @@ def main():
   for k in ('b_fused_stochastic', 'b_fused_deterministic', 'c_unfused_eager', 'c_unfused_graph'):
     if 'median' in res.get(k, {}):
       res[k]['over_a'] = round(res[k]['median'] / ra, 3)
-  print(json.dumps(res))
+  emit(res)
 
 
 if __name__ == '__main__':

@@ -21,27 +21,17 @@ Prints one JSON line per net (microseconds per env step of the whole batch).
 
     python tools/population_bench.py [--members 4096] [--runs 5] [--ab]
 """
-import argparse
-import json
 import math
-import os
-import sys
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-from brax_amd import envs  # noqa: E402
-from brax_amd.envs.evaluator import eval_rollout  # noqa: E402
-from brax_amd.envs.policy import MLPPolicy  # noqa: E402
-from brax_amd.envs.population import PolicyPopulation, population_rollout  # noqa: E402
-from tools.eval_bench import timed  # noqa: E402
-
-EP = 1000
+from eval_bench import EP, evaluation
+from measure import emit, start, tool_args
 
 
 def net(env, dev, which):
+  from brax_amd.envs.policy import MLPPolicy  # pylint: disable=import-outside-toplevel
   O, A = env.observation_size, env.action_size
   g = torch.Generator(device='cpu').manual_seed(0)
   if which == 'ars_linear':
@@ -56,14 +46,15 @@ def net(env, dev, which):
 
 
 def main():
-  ap = argparse.ArgumentParser()
+  ap = tool_args(__doc__, runs=5)
   ap.add_argument('--members', type=int, default=4096)
-  ap.add_argument('--runs', type=int, default=5)
   ap.add_argument('--warmup', type=int, default=1)
   ap.add_argument('--ab', action='store_true')
   ap.add_argument('--nets', nargs='+', default=['es_default', 'ars_linear'])
-  a = ap.parse_args()
-  dev = torch.device('cuda', 0)
+  a, dev = start('population_bench', ap)
+  from brax_amd import envs  # pylint: disable=import-outside-toplevel
+  from brax_amd.envs.evaluator import eval_rollout  # pylint: disable=import-outside-toplevel
+  from brax_amd.envs.population import PolicyPopulation, population_rollout  # pylint: disable=import-outside-toplevel
   B = a.members
   eval_env = envs.create('ant', batch_size=B, episode_length=EP, auto_reset=True,
                          eval_metrics=True, device=dev)
@@ -75,9 +66,7 @@ def main():
            'episode_length': EP, 'runs': a.runs, 'unit': 'us per env step (whole batch)'}
 
     def record(name, run):
-      med, lo, hi, peak = timed(run, a.runs, a.warmup)
-      res[name] = {'median': round(med / EP * 1e6, 3), 'min': round(lo / EP * 1e6, 3),
-                   'max': round(hi / EP * 1e6, 3), 'peak_MiB': round(peak / 2**20, 1)}
+      res[name] = evaluation(run, a.runs, a.warmup, dev)
 
     _, r = population_rollout(eval_env, st0, pp, k=EP, fused=True)
     res['staged'] = r.staged
@@ -92,7 +81,7 @@ def main():
     ra = res['a_population_fused']['median']
     res['a_over_b'] = round(ra / res['b_eval_shared_policy']['median'], 3)
     res['a_over_c'] = round(ra / res['c_population_chained']['median'], 4)
-    print(json.dumps(res), flush=True)
+    emit(res)
 
 
 if __name__ == '__main__':

@@ -22,45 +22,21 @@ Prints one JSON line per measurement.
 
     python tools/ppo_head_bench.py [--parts head,launches,ppo,split] [--runs 7] [--calls 100]
 """
-import argparse
 import functools
-import json
-import os
-import statistics
-import sys
-import time
 
-import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from measure import (ANT_PPO, alternate, device_kernels, emit, parts_of, ppo_learner, split_by_owner,
+                     spread, start, timed, tool_args)
 
-from brax_amd import envs  # noqa: E402
-from brax_amd.training import ppo  # noqa: E402
-from brax_amd.training.losses import Transition  # noqa: E402
-
-ANT = dict(num_envs=2048, unroll_length=5, batch_size=1024, num_minibatches=32,
-           num_updates_per_batch=8, learning_rate=3e-4, entropy_cost=1e-2, discounting=0.97,
-           reward_scaling=10.0, normalize_observations=True)
 SHAPE = (5, 1024, 8)
-
-
-def spread(xs, scale=1.0, digits=2):
-  return {'median': round(statistics.median(xs) * scale, digits),
-          'min': round(min(xs) * scale, digits), 'max': round(max(xs) * scale, digits)}
-
-
-def region(fn, calls, dev):
-  torch.cuda.synchronize(dev)
-  t = time.perf_counter()
-  for _ in range(calls):
-    fn()
-  torch.cuda.synchronize(dev)
-  return (time.perf_counter() - t) / calls
+OWNERS = (('ppo_head', 'head kernels'), ('mlp_', 'network kernels'), ('compute_gae', 'gae kernel'),
+          (('multi_tensor', 'adam'), 'adam'), 'other torch')
 
 
 def _forms(dev):
   from brax_amd.training import ppo_head  # pylint: disable=import-outside-toplevel
+  from brax_amd.training.losses import Transition  # pylint: disable=import-outside-toplevel
   T, B, A = SHAPE
   g = torch.Generator().manual_seed(0)
   r = lambda *s: torch.randn(s, generator=g).to(dev).transpose(0, 1)  # noqa: E731 ([B, T] views)
@@ -80,59 +56,26 @@ def _forms(dev):
 
 
 def bench_head(dev, runs, calls):
-  forms = _forms(dev)
-  times = {k: [] for k in forms}
-  for fn in forms.values():
-    region(fn, calls, dev)  # warm-up
-  for _ in range(runs):
-    for k, fn in forms.items():
-      times[k].append(region(fn, calls, dev))
+  times = alternate(_forms(dev), runs, calls, dev)
   res = {'measure': 'ppo_head_forward_backward', 'shape_T_B_A': list(SHAPE),
          'unit': 'us per iteration', 'runs': runs, 'calls_per_region': calls}
   res.update({k: spread(v, 1e6) for k, v in times.items()})
   res['chained_over_fused'] = round(res['chained']['median'] / res['fused']['median'], 2)
-  print(json.dumps(res), flush=True)
-
-
-def _kernels(fn, dev, repeat=1):
-  from torch.autograd import DeviceType  # pylint: disable=import-outside-toplevel
-  from torch.profiler import ProfilerActivity, profile  # pylint: disable=import-outside-toplevel
-  torch.cuda.synchronize(dev)
-  with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-    for _ in range(repeat):
-      fn()
-    torch.cuda.synchronize(dev)
-  return [e for e in prof.events() if e.device_type == DeviceType.CUDA
-          and not e.name.lower().startswith(('memcpy', 'memset'))]
+  emit(res)
 
 
 def count_launches(dev):
   res = {'measure': 'launches_per_iteration', 'shape_T_B_A': list(SHAPE)}
   for form, fn in _forms(dev).items():
     fn()
-    kernels = _kernels(fn, dev, repeat=4)
+    kernels = device_kernels(fn, dev, repeat=4)
     res[form] = len(kernels) / 4
     res[form + '_kernels'] = sorted({e.name[:60] for e in kernels})[:12]
-  print(json.dumps(res), flush=True)
-
-
-def _timed(fn, dev):
-  torch.cuda.synchronize(dev)
-  t = time.perf_counter()
-  r = fn()
-  torch.cuda.synchronize(dev)
-  return time.perf_counter() - t, r
-
-
-def _learner(dev):
-  env = envs.create('ant', episode_length=1000, batch_size=ANT['num_envs'], device=dev)
-  learner = ppo.Learner(env, device=dev, seed=0, fused_mlp=True, **ANT)
-  learner.reset(np.array([0, 1], np.uint32))
-  return learner
+  emit(res)
 
 
 def bench_ppo(dev, steps, parent):
-  learner = _learner(dev)
+  learner = ppo_learner(dev, fused_mlp=True)
   forms = ('parent',) if parent else ('fused_head', 'chained_head')
 
   def update(form):
@@ -140,7 +83,7 @@ def bench_ppo(dev, steps, parent):
       learner.fused_head = form == 'fused_head'
     data = learner.collect()
     learner.update_normalizer(data)
-    t, metrics = _timed(lambda: learner.update(data), dev)
+    t, metrics = timed(lambda: learner.update(data), dev)
     return t, float(metrics['total_loss'])
   for form in forms:
     update(form)  # warm-up: code objects, the allocator, Adam's state
@@ -148,8 +91,8 @@ def bench_ppo(dev, steps, parent):
   for _ in range(steps):
     for form in forms:
       rec[form].append(update(form))
-  n = ANT['num_updates_per_batch'] * ANT['num_minibatches']
-  res = {'measure': 'ppo_update_phase', 'env': 'ant', **ANT, 'fused_mlp': True, 'unit': 'ms',
+  n = ANT_PPO['num_updates_per_batch'] * ANT_PPO['num_minibatches']
+  res = {'measure': 'ppo_update_phase', 'env': 'ant', **ANT_PPO, 'fused_mlp': True, 'unit': 'ms',
          'steps': steps, 'adam_steps': n}
   for form in forms:
     res[form] = spread([t for t, _ in rec[form]], 1e3)
@@ -157,53 +100,30 @@ def bench_ppo(dev, steps, parent):
     res[form + '_last_total_loss'] = rec[form][-1][1]
   if not parent:
     res['chained_over_fused'] = round(res['chained_head']['median'] / res['fused_head']['median'], 2)
-  print(json.dumps(res), flush=True)
-
-
-def _owner(name):
-  n = name.lower()
-  if 'ppo_head' in n:
-    return 'head kernels'
-  if 'mlp_' in n:
-    return 'network kernels'
-  if 'compute_gae' in n:
-    return 'gae kernel'
-  if 'multi_tensor' in n or 'adam' in n:
-    return 'adam'
-  return 'other torch'
+  emit(res)
 
 
 def split_update(dev):
-  learner = _learner(dev)
-  n = ANT['num_updates_per_batch'] * ANT['num_minibatches']
+  learner = ppo_learner(dev, fused_mlp=True)
+  n = ANT_PPO['num_updates_per_batch'] * ANT_PPO['num_minibatches']
   for form in (True, False):
     learner.fused_head = form
     data = learner.collect()
     learner.update_normalizer(data)
     learner.update(data)  # warm-up; the second update is profiled
-    kernels = _kernels(lambda: learner.update(data), dev)  # pylint: disable=cell-var-from-loop
+    # (this tool has always kept the `Optimizer.step#` spans: they match 'adam', so that row
+    # is torch's seven launches plus one span, and its time counts the seven twice)
+    kernels = device_kernels(lambda: learner.update(data), dev,  # pylint: disable=cell-var-from-loop
+                             skip=('memcpy', 'memset'))
     res = {'measure': 'ppo_update_split', 'fused_head': form, 'adam_steps': n,
-           'unit': 'per Adam step: launches, device us'}
-    for owner in ('network kernels', 'head kernels', 'gae kernel', 'adam', 'other torch'):
-      own = [e for e in kernels if _owner(e.name) == owner]
-      res[owner] = [round(len(own) / n, 1), round(sum(e.device_time for e in own) / n, 1)]
-    print(json.dumps(res), flush=True)
+           'unit': 'per Adam step: launches, device us', **split_by_owner(kernels, n, OWNERS)}
+    emit(res)
 
 
 def main():
-  ap = argparse.ArgumentParser()
-  ap.add_argument('--parts', default='head,launches,ppo,split')
-  ap.add_argument('--runs', type=int, default=7)
-  ap.add_argument('--calls', type=int, default=100)
-  ap.add_argument('--steps', type=int, default=3)
-  ap.add_argument('--parent', action='store_true')
-  a = ap.parse_args()
-  if not torch.cuda.is_available():
-    sys.exit('ppo_head_bench needs a GPU: a CPU run gives no time')
-  dev = torch.device('cuda', 0)
-  parts = a.parts.split(',')
-  if a.parent:
-    parts = [p for p in parts if p == 'ppo']
+  a, dev = start('ppo_head_bench', tool_args(__doc__, runs=7, calls=100, steps=3,
+                                             parts='head,launches,ppo,split'))
+  parts = parts_of(a, in_parent=('ppo',))
   if 'head' in parts:
     bench_head(dev, a.runs, a.calls)
   if 'launches' in parts:

@@ -21,53 +21,17 @@ Prints one JSON line per measurement.
 
     python tools/sac_bench.py [--runs 7] [--calls 50] [--steps 3] [--learn]
 """
-import argparse
 import functools
-import json
-import os
-import statistics
-import sys
 import time
 
-import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-from brax_amd import envs  # noqa: E402
-from brax_amd.envs import wrappers  # noqa: E402
-from brax_amd.envs.policy import fused_supported, policy_rollout  # noqa: E402
-from brax_amd.training import sac, sac_networks  # noqa: E402
-from brax_amd.training.replay_buffers import UniformSamplingQueue, transition_fields  # noqa: E402
-
-ANT_OBS, ANT_ACT = 87, 8
-
-
-def spread(xs, scale=1.0, digits=2):
-  return {'median': round(statistics.median(xs) * scale, digits),
-          'min': round(min(xs) * scale, digits), 'max': round(max(xs) * scale, digits)}
-
-
-def region(fn, calls, dev):
-  torch.cuda.synchronize(dev)
-  t = time.perf_counter()
-  for _ in range(calls):
-    fn()
-  torch.cuda.synchronize(dev)
-  return (time.perf_counter() - t) / calls
-
-
-def alternate(forms, runs, calls, dev):
-  times = {k: [] for k in forms}
-  for fn in forms.values():
-    region(fn, max(calls // 4, 1), dev)  # warm-up
-  for _ in range(runs):
-    for k, fn in forms.items():
-      times[k].append(region(fn, calls, dev))
-  return times
+from measure import (ANT_ACT, ANT_OBS, SAC_ANT, alternate, ant_env, emit, sac_learner, spread, start,
+                     timed, tool_args)
 
 
 def bench_buffer(dev, fields, capacity, n_insert, n_sample, runs, calls, label):
+  from brax_amd.training.replay_buffers import UniformSamplingQueue  # pylint: disable=import-outside-toplevel
   g = torch.Generator().manual_seed(capacity)
   q = {form: UniformSamplingQueue(capacity, fields, n_sample, seed=1, device=dev)
        for form in ('fused', 'chained')}
@@ -85,56 +49,50 @@ def bench_buffer(dev, fields, capacity, n_insert, n_sample, runs, calls, label):
   head = {'case': label, 'capacity': capacity, 'row_words': words, 'unit': 'us per call',
           'runs': runs, 'calls_per_region': calls}
   t = alternate({form: functools.partial(b.insert, batch, fused=flag[form]) for form, b in q.items()},
-                runs, calls, dev)
+                runs, calls, dev, warmup_calls=max(calls // 4, 1))
   res = {'measure': 'insert', **head, 'rows': n_insert, 'bit_identical': same,
          'bytes_moved': 2 * n_insert * words * 4}
   res.update({k: spread(v, 1e6) for k, v in t.items()})
   res['chained_over_fused'] = round(res['chained']['median'] / res['fused']['median'], 2)
   res['fused_GB_per_s'] = round(res['bytes_moved'] / res['fused']['median'] / 1e3, 1)
-  print(json.dumps(res), flush=True)
+  emit(res)
   t = alternate({form: functools.partial(b.sample, fused=flag[form], out=out[form])
-                 for form, b in q.items()}, runs, calls, dev)
+                 for form, b in q.items()}, runs, calls, dev, warmup_calls=max(calls // 4, 1))
   res = {'measure': 'sample', **head, 'rows': n_sample, 'bit_identical': same_sample,
          'bytes_moved': 2 * n_sample * words * 4}
   res.update({k: spread(v, 1e6) for k, v in t.items()})
   res['chained_over_fused'] = round(res['chained']['median'] / res['fused']['median'], 2)
   res['fused_GB_per_s'] = round(res['bytes_moved'] / res['fused']['median'] / 1e3, 1)
-  print(json.dumps(res), flush=True)
+  emit(res)
 
 
 def bench_step(dev, num_envs, batch_size, updates, hidden, steps):
-  env = envs.create('ant', episode_length=1000, batch_size=num_envs, device=dev)
-  factory = functools.partial(sac_networks.make_sac_networks, hidden_layer_sizes=hidden)
-  L = sac.Learner(env, num_envs, batch_size=batch_size, grad_updates_per_step=updates,
-                  max_replay_size=1 << 20, normalize_observations=True, seed=0,
-                  network_factory=factory, device=dev)
+  from brax_amd.envs.policy import fused_supported, policy_rollout  # pylint: disable=import-outside-toplevel
+  from brax_amd.training import sac_networks  # pylint: disable=import-outside-toplevel
+  env = ant_env(dev, num_envs)
+  # (the one SAC setup that starts on an empty queue and names its hidden sizes)
+  L = sac_learner(dev, env, prefill=0, num_envs=num_envs, batch_size=batch_size,
+                  grad_updates_per_step=updates,
+                  network_factory=functools.partial(sac_networks.make_sac_networks,
+                                                    hidden_layer_sizes=hidden))
   why = fused_supported(env, L.actor)
-  L.reset(wrappers.split_key(np.array([0, 0], np.uint32))[0])
 
   def phases(fused):
     out = {}
-
-    def timed(name, fn):
-      torch.cuda.synchronize(dev)
-      t = time.perf_counter()
-      r = fn()
-      torch.cuda.synchronize(dev)
-      out[name] = time.perf_counter() - t
-      return r
     obs0 = L.state.obs
 
     def act():
       r = policy_rollout(env, L.state, L.actor, 1, seed=L.seed, offset=L._noise_offset)  # pylint: disable=protected-access
       L._noise_offset += 2 * num_envs * env.action_size  # pylint: disable=protected-access
       return r
-    L.state, traj, extras = timed('act', act)
-    timed('normaliser', lambda: L.normalizer.update(obs0))
+    out['act'], (L.state, traj, extras) = timed(act, dev)
+    out['normaliser'], _ = timed(lambda: L.normalizer.update(obs0), dev)
     row = {'observation': obs0, 'action': extras.action[0], 'reward': traj.reward[0],
            'discount': 1 - traj.done[0], 'next_observation': traj.obs[0],
            'truncation': traj.truncation[0]}
-    timed('insert', lambda: L.buffer.insert(row, fused=fused))
-    sample = timed('sample', lambda: L.buffer.sample(fused=fused))
-    timed('updates', lambda: L.update(sample))
+    out['insert'], _ = timed(lambda: L.buffer.insert(row, fused=fused), dev)
+    out['sample'], sample = timed(lambda: L.buffer.sample(fused=fused), dev)
+    out['updates'], _ = timed(lambda: L.update(sample), dev)
     return out
   phases(None), phases(False)  # warm-up
   rec = {None: [], False: []}
@@ -153,16 +111,17 @@ def bench_step(dev, num_envs, batch_size, updates, hidden, steps):
   total = lambda recs: [sum(r.values()) for r in recs]  # noqa: E731
   res['step_fused'] = spread(total(rec[None]), 1e3, 3)
   res['step_chained'] = spread(total(rec[False]), 1e3, 3)
-  print(json.dumps(res), flush=True)
+  emit(res)
 
 
 def learn(dev, num_timesteps, num_evals):
+  from brax_amd.training import sac, sac_networks  # pylint: disable=import-outside-toplevel
   curve = []
 
   def progress(step, m):
     curve.append({'env_steps': step, 'eval/episode_reward': round(float(m['eval/episode_reward']), 2),
                   'eval/avg_episode_length': round(float(m['eval/avg_episode_length']), 1)})
-    print(json.dumps({'measure': 'learn_progress', 'agent': 'sac', **curve[-1]}), flush=True)
+    emit({'measure': 'learn_progress', 'agent': 'sac', **curve[-1]})
   cfg = dict(num_envs=64, batch_size=128, grad_updates_per_step=4, min_replay_size=1024,
              max_replay_size=1 << 16, learning_rate=6e-4, discounting=0.99,
              normalize_observations=True)
@@ -173,34 +132,28 @@ def learn(dev, num_timesteps, num_evals):
       seed=1, num_evals=num_evals, device=dev, progress_fn=progress,
       network_factory=functools.partial(sac_networks.make_sac_networks, hidden_layer_sizes=hidden),
       **cfg)
-  print(json.dumps({'measure': 'learn', 'agent': 'sac', 'env': 'inverted_pendulum', **cfg,
-                    'hidden': list(hidden), 'num_timesteps': num_timesteps,
-                    'wall_s': round(time.perf_counter() - t, 1),
-                    'training/sps': round(float(metrics['training/sps'])), 'curve': curve}),
-        flush=True)
+  emit({'measure': 'learn', 'agent': 'sac', 'env': 'inverted_pendulum', **cfg,
+        'hidden': list(hidden), 'num_timesteps': num_timesteps,
+        'wall_s': round(time.perf_counter() - t, 1),
+        'training/sps': round(float(metrics['training/sps'])), 'curve': curve})
 
 
 def main():
-  ap = argparse.ArgumentParser()
-  ap.add_argument('--runs', type=int, default=7)
-  ap.add_argument('--calls', type=int, default=50)
-  ap.add_argument('--steps', type=int, default=3)
-  ap.add_argument('--envs', type=int, default=4096)
-  ap.add_argument('--updates', type=int, default=64)
+  ap = tool_args(__doc__, runs=7, calls=50, steps=3)
+  ap.add_argument('--envs', type=int, default=SAC_ANT['num_envs'])
+  ap.add_argument('--updates', type=int, default=SAC_ANT['updates'])
   ap.add_argument('--learn', action='store_true')
   ap.add_argument('--learn-timesteps', type=int, default=40_000)
   ap.add_argument('--learn-evals', type=int, default=6)
   ap.add_argument('--skip-step', action='store_true')
-  a = ap.parse_args()
-  if not torch.cuda.is_available():
-    sys.exit('sac_bench needs a GPU: a CPU run gives no time')
-  dev = torch.device('cuda', 0)
+  a, dev = start('sac_bench', ap)
+  from brax_amd.training.replay_buffers import transition_fields  # pylint: disable=import-outside-toplevel
   bench_buffer(dev, transition_fields(ANT_OBS, ANT_ACT), 1 << 20, 4096, 256 * 64, a.runs, a.calls,
                'ant')
   bench_buffer(dev, {'a': 1, 'b': 3}, 10, 2, 2, a.runs, a.calls, "the reference's buffer test")
   if not a.skip_step:
     for hidden in ((256, 256), (128, 128)):
-      bench_step(dev, a.envs, 256, a.updates, hidden, a.steps)
+      bench_step(dev, a.envs, SAC_ANT['batch_size'], a.updates, hidden, a.steps)
   if a.learn:
     learn(dev, a.learn_timesteps, a.learn_evals)
 

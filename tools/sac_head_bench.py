@@ -21,66 +21,15 @@ Prints one JSON line per measurement.
 
     python tools/sac_head_bench.py [--parts head,sac,split] [--runs 7] [--calls 50]
 """
-import argparse
 import collections
-import json
-import os
-import statistics
-import sys
-import time
 
-import numpy as np
 import torch
 
-SAC = dict(num_envs=4096, batch_size=256, updates=64)
-ANT_OBS, ANT_ACT = 87, 8
-OWNERS = ('network kernels', 'head kernels', 'optimiser', 'other torch')
+from measure import (ANT_ACT, ANT_OBS, SAC_ANT, all_kernels, alternate, ant_env, device_kernels, emit,
+                     owner_of, parts_of, sac_learner, split_by_owner, spread, start, timed, tool_args)
 
-
-def spread(xs, scale=1.0, digits=2):
-  return {'median': round(statistics.median(xs) * scale, digits),
-          'min': round(min(xs) * scale, digits), 'max': round(max(xs) * scale, digits)}
-
-
-def region(fn, calls, dev):
-  torch.cuda.synchronize(dev)
-  t = time.perf_counter()
-  for _ in range(calls):
-    fn()
-  torch.cuda.synchronize(dev)
-  return (time.perf_counter() - t) / calls
-
-
-def _kernels(fn, dev, repeat=1):
-  from torch.autograd import DeviceType  # pylint: disable=import-outside-toplevel
-  from torch.profiler import ProfilerActivity, profile  # pylint: disable=import-outside-toplevel
-  torch.cuda.synchronize(dev)
-  with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-    for _ in range(repeat):
-      fn()
-    torch.cuda.synchronize(dev)
-  return [e for e in prof.events() if e.device_type == DeviceType.CUDA
-          and not e.name.lower().startswith(('memcpy', 'memset', 'optimizer.'))]
-
-
-def _owner(name):
-  n = name.lower()
-  if 'sac_head' in n:
-    return 'head kernels'
-  if 'mlp_' in n:
-    return 'network kernels'
-  if 'multi_tensor' in n or 'adam' in n:
-    return 'optimiser'
-  return 'other torch'
-
-
-def _split(kernels, n):
-  res = {}
-  for owner in OWNERS:
-    own = [e for e in kernels if _owner(e.name) == owner]
-    res[owner] = [round(len(own) / n, 1), round(sum(e.device_time for e in own) / n, 1)]
-  res['all'] = [round(len(kernels) / n, 1), round(sum(e.device_time for e in kernels) / n, 1)]
-  return res
+OWNERS = (('sac_head', 'head kernels'), ('mlp_', 'network kernels'),
+          (('multi_tensor', 'adam'), 'optimiser'), 'other torch')
 
 
 def bench_head(dev, runs, calls):
@@ -96,43 +45,29 @@ def bench_head(dev, runs, calls):
     args = (ts, normalizer, trans, eps, 30.0, 0.997, True)
     forms = {'chained': lambda: sac._chained_gradients(*args),  # pylint: disable=protected-access
              'fused': lambda: sac_head.gradients(*args)}
-    times = {k: [] for k in forms}
-    for fn in forms.values():
-      region(fn, calls, dev)  # warm-up
-    for _ in range(runs):
-      for k, fn in forms.items():
-        times[k].append(region(fn, calls, dev))
+    times = alternate(forms, runs, calls, dev)
     res = {'measure': 'sac_gradients', 'B': B, 'O': ANT_OBS, 'A': ANT_ACT, 'C': 2,
            'hidden': [256, 256], 'fused_mlp': True, 'unit': 'us per call', 'runs': runs,
            'calls_per_region': calls}
     res.update({k: spread(v, 1e6) for k, v in times.items()})
     res['chained_over_fused'] = round(res['chained']['median'] / res['fused']['median'], 2)
-    print(json.dumps(res), flush=True)
+    emit(res)
     for form, fn in forms.items():
-      kernels = _kernels(fn, dev, repeat=4)
-      print(json.dumps({'measure': 'sac_gradients_launches', 'B': B, 'form': form,
-                        'unit': 'per call: launches, device us', **_split(kernels, 4)}), flush=True)
+      kernels = device_kernels(fn, dev, repeat=4)
+      emit({'measure': 'sac_gradients_launches', 'B': B, 'form': form,
+            'unit': 'per call: launches, device us', **split_by_owner(kernels, 4, OWNERS),
+            'all': all_kernels(kernels, 4)})
 
 
 def _learners(dev, parent):
-  from brax_amd import envs  # pylint: disable=import-outside-toplevel
-  from brax_amd.envs import wrappers  # pylint: disable=import-outside-toplevel
-  from brax_amd.training import sac, sac_networks  # pylint: disable=import-outside-toplevel
-  env = envs.create('ant', episode_length=1000, batch_size=SAC['num_envs'], device=dev)
+  """(this tool alone sets the learning rate, the discount and the reward
+  scale of the README's SAC run; the others leave `sac.Learner`'s defaults)"""
+  env = ant_env(dev, SAC_ANT['num_envs'])
   forms = {'parent': {}} if parent else {'fused_head': dict(fused_head=True),
                                          'chained_head': dict(fused_head=False)}
-  out = {}
-  for form, kw in forms.items():
-    L = sac.Learner(env, SAC['num_envs'], batch_size=SAC['batch_size'],
-                    grad_updates_per_step=SAC['updates'], max_replay_size=1 << 20,
-                    learning_rate=6e-4, discounting=0.997, reward_scaling=30.0,
-                    normalize_observations=True, seed=0, fused_mlp=True, fused_adam=True,
-                    network_factory=sac_networks.make_sac_networks, device=dev, **kw)
-    L.reset(wrappers.split_key(np.array([0, 0], np.uint32))[0])
-    for _ in range(4):
-      L.get_experience()
-    out[form] = L
-  return out
+  return {form: sac_learner(dev, env, learning_rate=6e-4, discounting=0.997, reward_scaling=30.0,
+                            fused_mlp=True, fused_adam=True, **kw)
+          for form, kw in forms.items()}
 
 
 def bench_sac(dev, steps, parent):
@@ -142,60 +77,49 @@ def bench_sac(dev, steps, parent):
     L = learners[form]
     L.get_experience()
     sample = L.buffer.sample()
-    torch.cuda.synchronize(dev)
-    t = time.perf_counter()
-    metrics = L.update(sample)
-    torch.cuda.synchronize(dev)
-    return time.perf_counter() - t, float(metrics['critic_loss'])
+    t, metrics = timed(lambda: L.update(sample), dev)
+    return t, float(metrics['critic_loss'])
   for form in learners:
     update(form)  # warm-up: code objects, the allocator, Adam's state
   rec = {form: [] for form in learners}
   for _ in range(steps):
     for form in learners:
       rec[form].append(update(form))
-  res = {'measure': 'sac_gradient_updates', 'env': 'ant', **SAC, 'hidden': [256, 256],
+  res = {'measure': 'sac_gradient_updates', 'env': 'ant', **SAC_ANT, 'hidden': [256, 256],
          'fused_mlp': True, 'fused_adam': True, 'unit': 'ms', 'steps': steps}
   for form in learners:
     res[form] = spread([t for t, _ in rec[form]], 1e3)
-    res[form + '_ms_per_update'] = round(res[form]['median'] / SAC['updates'], 3)
+    res[form + '_ms_per_update'] = round(res[form]['median'] / SAC_ANT['updates'], 3)
     res[form + '_last_critic_loss'] = rec[form][-1][1]
   if not parent:
     res['chained_over_fused'] = round(res['chained_head']['median'] / res['fused_head']['median'], 2)
-  print(json.dumps(res), flush=True)
+  emit(res)
 
 
 def split_updates(dev):
+  n = SAC_ANT['updates']
   for form, L in _learners(dev, False).items():
     L.get_experience()
     sample = L.buffer.sample()
     L.update(sample)  # warm-up; the second update is profiled
-    kernels = _kernels(lambda: L.update(sample), dev)  # pylint: disable=cell-var-from-loop
-    res = {'measure': 'sac_update_split', 'form': form, 'gradient_steps': SAC['updates'],
-           'unit': 'per gradient step: launches, device us', **_split(kernels, SAC['updates'])}
+    kernels = device_kernels(lambda: L.update(sample), dev)  # pylint: disable=cell-var-from-loop
+    res = {'measure': 'sac_update_split', 'form': form, 'gradient_steps': n,
+           'unit': 'per gradient step: launches, device us',
+           **split_by_owner(kernels, n, OWNERS), 'all': all_kernels(kernels, n)}
     if form == 'fused_head':
-      other = collections.Counter(e.name[:70] for e in kernels if _owner(e.name) == 'other torch')
-      res['other_torch_per_step'] = {k: round(v / SAC['updates'], 2) for k, v in other.most_common()}
-      head = collections.Counter(e.name[:50] for e in kernels if _owner(e.name) == 'head kernels')
-      res['head_kernels_per_step'] = {k: round(v / SAC['updates'], 2) for k, v in head.items()}
-    print(json.dumps(res), flush=True)
+      names = lambda owner, width: collections.Counter(  # noqa: E731
+          e.name[:width] for e in kernels if owner_of(e.name, OWNERS) == owner)
+      res['other_torch_per_step'] = {k: round(v / n, 2)
+                                     for k, v in names('other torch', 70).most_common()}
+      res['head_kernels_per_step'] = {k: round(v / n, 2)
+                                      for k, v in names('head kernels', 50).items()}
+    emit(res)
 
 
 def main():
-  ap = argparse.ArgumentParser()
-  ap.add_argument('--parts', default='head,sac,split')
-  ap.add_argument('--runs', type=int, default=7)
-  ap.add_argument('--calls', type=int, default=50)
-  ap.add_argument('--steps', type=int, default=5)
-  ap.add_argument('--parent', action='store_true')
-  ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-  a = ap.parse_args()
-  sys.path.insert(0, os.path.abspath(a.root))
-  if not torch.cuda.is_available():
-    sys.exit('sac_head_bench needs a GPU: a CPU run gives no time')
-  dev = torch.device('cuda', 0)
-  parts = a.parts.split(',')
-  if a.parent:
-    parts = [p for p in parts if p == 'sac']
+  a, dev = start('sac_head_bench', tool_args(__doc__, runs=7, calls=50, steps=5,
+                                             parts='head,sac,split'))
+  parts = parts_of(a, in_parent=('sac',))
   if 'head' in parts:
     bench_head(dev, a.runs, a.calls)
   if 'sac' in parts:
