@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import subprocess
 
-from brax_amd import abi
+from brax_amd import abi, abi_mlp_group
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('BRAX_AMD_LIB') or os.path.join(HERE, '_lib', 'libbrax_amd.so')
@@ -27,6 +27,8 @@ _lib = None
 
 _SIGS = abi.SIGNATURES  # name -> (argtypes, restype), from the one table abi.ARGS
 EXPORTS = tuple(_SIGS)
+# the headers on top of it (include/brax_amd_mlp_group.h), each with its own table
+_MORE_SIGS = abi_mlp_group.SIGNATURES
 # what an argument nobody names is: a null pointer, a zero scalar
 _UNNAMED = {name: tuple(0 if issubclass(t, C._SimpleCData) and t is not C.c_void_p else None
                         for _, t in sig) for name, sig in abi.ARGS.items()}
@@ -54,7 +56,7 @@ def lib():
           '(run __graft_entry__.build() or make -C brax_amd/csrc). '
           'brax_amd has no CPU fallback.')
     l = C.CDLL(LIB_PATH)
-    for name, (args, res) in _SIGS.items():
+    for name, (args, res) in {**_SIGS, **_MORE_SIGS}.items():
       f = getattr(l, name)
       f.argtypes = args
       f.restype = res

@@ -3,6 +3,7 @@
 // the MLPs, the PPO and SAC loss heads and the optimiser step, none on a system
 #include <algorithm>
 #include <initializer_list>
+#include <string>
 
 #include "bx_capi_common.h"
 #include "mlp_launch.h"
@@ -133,6 +134,58 @@ int mlp_args(const bx_mlp* net, int64_t rows, int64_t x_stride, MlpNet* m) {
                 std::to_string(net->in[0]));
   return 0;
 }
+
+// what bx_mlp_forward refuses after mlp_args (rows > 0), and bx_mlp_backward
+// likewise: the single and the group entry points make the same checks
+int mlp_forward_ptrs(const float* x, const float* y) {
+  if (!x || !y) return fail("null argument");
+  return 0;
+}
+int64_t mlp_workspace_need(const MlpNet& m, int64_t rows) {
+  return std::max<int64_t>(16, 4 * rows * (int64_t)m.hidden);
+}
+int mlp_backward_ptrs(const MlpNet& m, const float* x, const float* saved, const float* dy,
+                      const void* workspace, int64_t bytes, int64_t need) {
+  if (!x || !dy) return fail("null argument");
+  if (m.n_layers > 1 && !saved) return fail("null saved with hidden layers");
+  return check_workspace(workspace, bytes, need, 16);
+}
+void mlp_grads(const MlpNet& m, const bx_mlp_grads* grads, MlpGrads* g) {
+  if (grads)
+    for (int l = 0; l < m.n_layers; ++l) {
+      g->dw[l] = grads->dw[l];
+      g->db[l] = grads->db[l];
+    }
+}
+
+// a group's members: the count, and the last refusal as member i's
+int mlp_group_count(const bx_mlp_member* members, int32_t n_members) {
+  if (!members) return fail("null argument");
+  if (n_members < 1 || n_members > BX_MLP_MAX_GROUP)
+    return fail("n_members " + std::to_string(n_members) + " outside 1.." +
+                std::to_string(BX_MLP_MAX_GROUP));
+  return 0;
+}
+int member_fail(int i) {
+  return fail("member " + std::to_string(i) + ": " + std::string(bx_last_error()));
+}
+// the arrays a group launch writes: no two members may name the same one (a
+// member has at most dx, its workspace and a dw and a db per layer)
+struct MlpWritten {
+  struct Entry { const void* p; int member; const char* what; };
+  Entry entries[BX_MLP_MAX_GROUP * (2 + 2 * BX_MLP_MAX_LAYERS)];
+  int n = 0;
+  int add(const void* p, int member, const char* what) {
+    if (!p) return 0;
+    for (int k = 0; k < n; ++k)
+      if (entries[k].p == p && entries[k].member != member)
+        return fail("members " + std::to_string(entries[k].member) + " and " +
+                    std::to_string(member) + " write the same array (" + entries[k].what + ", " +
+                    what + ")");
+    entries[n++] = {p, member, what};
+    return 0;
+  }
+};
 
 // the SAC heads' shared checks: the row count, then the action count
 int sac_rows(int64_t n_rows) {
@@ -305,7 +358,7 @@ int bx_mlp_forward(const bx_mlp* net, int64_t rows, const float* x, int64_t x_st
   MlpNet m{};
   if (mlp_args(net, rows, x_stride, &m)) return 1;
   if (rows == 0) return 0;
-  if (!x || !y) return fail("null argument");
+  if (mlp_forward_ptrs(x, y)) return 1;
   STREAM_SCOPE(stream, st);
   HIP_OK(launch_mlp_forward(m, rows, x, x_stride, y, saved, st));
   return 0;
@@ -317,20 +370,83 @@ int bx_mlp_backward(const bx_mlp* net, int64_t rows, const float* x, int64_t x_s
   if (!workspace_bytes) return fail("null argument");
   MlpNet m{};
   if (mlp_args(net, rows, x_stride, &m)) return 1;
-  const int64_t need = std::max<int64_t>(16, 4 * rows * (int64_t)m.hidden);
+  const int64_t need = mlp_workspace_need(m, rows);
   if (size_query(workspace, workspace_bytes, need)) return 0;
   if (rows == 0) return 0;
-  if (!x || !dy) return fail("null argument");
-  if (m.n_layers > 1 && !saved) return fail("null saved with hidden layers");
-  if (check_workspace(workspace, *workspace_bytes, need, 16)) return 1;
+  if (mlp_backward_ptrs(m, x, saved, dy, workspace, *workspace_bytes, need)) return 1;
   MlpGrads g{};
-  if (grads)
-    for (int l = 0; l < m.n_layers; ++l) {
-      g.dw[l] = grads->dw[l];
-      g.db[l] = grads->db[l];
-    }
+  mlp_grads(m, grads, &g);
   STREAM_SCOPE(stream, st);
   HIP_OK(launch_mlp_backward(m, g, rows, x, x_stride, saved, dy, dx, (float*)workspace, st));
+  return 0;
+}
+
+int bx_mlp_group_sizes(int32_t* member_bytes) {
+  if (!member_bytes) return fail("null argument");
+  *member_bytes = (int32_t)sizeof(bx_mlp_member);
+  return 0;
+}
+
+int bx_mlp_group_forward(const bx_mlp_member* members, int32_t n_members, void* stream) {
+  if (mlp_group_count(members, n_members)) return 1;
+  MlpForwardMember table[BX_MLP_MAX_GROUP] = {};
+  MlpWritten written;
+  int n = 0;
+  for (int i = 0; i < n_members; ++i) {
+    const bx_mlp_member& s = members[i];
+    MlpForwardMember& d = table[n];
+    if (mlp_args(s.net, s.rows, s.x_stride, &d.net)) return member_fail(i);
+    if (s.rows == 0) continue;
+    if (mlp_forward_ptrs(s.x, s.y)) return member_fail(i);
+    if (written.add(s.y, i, "y") || written.add(s.saved, i, "saved")) return 1;
+    d.rows = s.rows;
+    d.x = s.x;
+    d.x_stride = s.x_stride;
+    d.y = s.y;
+    d.saved = s.saved;
+    ++n;
+  }
+  if (n == 0) return 0;
+  STREAM_SCOPE(stream, st);
+  HIP_OK(launch_mlp_group_forward(table, n, st));
+  return 0;
+}
+
+int bx_mlp_group_backward(bx_mlp_member* members, int32_t n_members, int32_t query, void* stream) {
+  if (mlp_group_count(members, n_members)) return 1;
+  MlpGradMember table[BX_MLP_MAX_GROUP] = {};
+  float* dx[BX_MLP_MAX_GROUP] = {};
+  MlpWritten written;
+  int n = 0;
+  for (int i = 0; i < n_members; ++i) {
+    bx_mlp_member& s = members[i];
+    MlpGradMember& d = table[n];
+    d = MlpGradMember{};
+    if (mlp_args(s.net, s.rows, s.x_stride, &d.net)) return member_fail(i);
+    const int64_t need = mlp_workspace_need(d.net, s.rows);
+    if (query) {
+      s.workspace_bytes = need;
+      continue;
+    }
+    if (s.rows == 0 || !s.dy) continue;
+    if (mlp_backward_ptrs(d.net, s.x, s.saved, s.dy, s.workspace, s.workspace_bytes, need))
+      return member_fail(i);
+    mlp_grads(d.net, s.grads, &d.grads);
+    if (written.add(s.dx, i, "dx") || written.add(s.workspace, i, "workspace")) return 1;
+    for (int l = 0; l < d.net.n_layers; ++l)
+      if (written.add(d.grads.dw[l], i, "dw") || written.add(d.grads.db[l], i, "db")) return 1;
+    d.rows = s.rows;
+    d.x = s.x;
+    d.x_stride = s.x_stride;
+    d.saved = s.saved;
+    d.dy = s.dy;
+    d.dz = (const float*)s.workspace;
+    dx[n] = s.dx;
+    ++n;
+  }
+  if (n == 0) return 0;
+  STREAM_SCOPE(stream, st);
+  HIP_OK(launch_mlp_group_backward(table, dx, n, st));
   return 0;
 }
 

@@ -140,14 +140,14 @@ __device__ __forceinline__ void clear(f32x16 (&acc)[2]) {
 
 // ---- forward: every layer of a 32-row tile in one launch ------------------------------------
 
-__global__ void __launch_bounds__(256) mlp_forward_kernel(MlpNet net, int64_t rows,
-                                                          const float* __restrict__ x,
-                                                          int64_t x_stride, float* __restrict__ y,
-                                                          float* __restrict__ saved) {
-  __shared__ __attribute__((aligned(16))) float image[TM * LDW];
+// (the tile bodies are __device__ functions: the single-network kernels and
+// the group kernels below run the same code on a tile, in the same order)
+__device__ __forceinline__ void forward_tile(const MlpNet& net, int64_t rows,
+                                             const float* __restrict__ x, int64_t x_stride,
+                                             float* __restrict__ y, float* __restrict__ saved,
+                                             float* image, int64_t row0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31, h = lane >> 5;
-  const int64_t row0 = (int64_t)blockIdx.x * TM;
   const int L = net.n_layers, kind = net.activation;
   for (int l = 0; l < L; ++l) {
     const int K = net.in[l], N = net.out[l];
@@ -193,21 +193,40 @@ __global__ void __launch_bounds__(256) mlp_forward_kernel(MlpNet net, int64_t ro
   }
 }
 
+__global__ void __launch_bounds__(256) mlp_forward_kernel(MlpNet net, int64_t rows,
+                                                          const float* __restrict__ x,
+                                                          int64_t x_stride, float* __restrict__ y,
+                                                          float* __restrict__ saved) {
+  __shared__ __attribute__((aligned(16))) float image[TM * LDW];
+  forward_tile(net, rows, x, x_stride, y, saved, image, (int64_t)blockIdx.x * TM);
+}
+
+// A group launch: workgroup b belongs to the member m with first[m] <= b <
+// first[m + 1] (the walk mlp_grad_kernel does over its layers) and is that
+// member's tile b - first[m]. The member table travels in the kernel
+// arguments.
+__global__ void __launch_bounds__(256) mlp_group_forward_kernel(MlpGroupForward g) {
+  __shared__ __attribute__((aligned(16))) float image[TM * LDW];
+  int m = 0;
+  while ((int)blockIdx.x >= g.first[m + 1]) ++m;
+  const MlpForwardMember& M = g.m[m];
+  forward_tile(M.net, M.rows, M.x, M.x_stride, M.y, M.saved, image,
+               (int64_t)((int)blockIdx.x - g.first[m]) * TM);
+}
+
 // ---- backward (i): the reverse chain of a 32-row tile ----------------------------------------
 // The image holds dz_l (dy for the last layer). g = dz_l . W_l^T is the
 // gradient of layer l - 1's activations; dz_{l-1} = g * act'(z_{l-1}) goes to
 // the workspace (rows, hidden) for launch (ii) and back into the image. With
 // `dx` the chain ends in dz_0 . W_0^T, 256 columns of the input at a time.
 
-__global__ void __launch_bounds__(256) mlp_backward_kernel(MlpNet net, int64_t rows,
-                                                           const float* __restrict__ saved,
-                                                           const float* __restrict__ dy,
-                                                           float* __restrict__ dx,
-                                                           float* __restrict__ dz, uint32_t vec_mask) {
-  __shared__ __attribute__((aligned(16))) float image[TM * LDW];
+__device__ __forceinline__ void backward_tile(const MlpNet& net, int64_t rows,
+                                              const float* __restrict__ saved,
+                                              const float* __restrict__ dy, float* __restrict__ dx,
+                                              float* __restrict__ dz, uint32_t vec_mask,
+                                              float* image, int64_t row0) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31, h = lane >> 5;
-  const int64_t row0 = (int64_t)blockIdx.x * TM;
   const int L = net.n_layers, kind = net.activation;
   fill_image(image, dy, net.out[L - 1], row0, rows, net.out[L - 1]);
   __syncthreads();
@@ -256,6 +275,24 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(MlpNet net, int64_t r
   }
 }
 
+__global__ void __launch_bounds__(256) mlp_backward_kernel(MlpNet net, int64_t rows,
+                                                           const float* __restrict__ saved,
+                                                           const float* __restrict__ dy,
+                                                           float* __restrict__ dx,
+                                                           float* __restrict__ dz, uint32_t vec_mask) {
+  __shared__ __attribute__((aligned(16))) float image[TM * LDW];
+  backward_tile(net, rows, saved, dy, dx, dz, vec_mask, image, (int64_t)blockIdx.x * TM);
+}
+
+__global__ void __launch_bounds__(256) mlp_group_backward_kernel(MlpGroupBackward g) {
+  __shared__ __attribute__((aligned(16))) float image[TM * LDW];
+  int m = 0;
+  while ((int)blockIdx.x >= g.first[m + 1]) ++m;
+  const MlpBackwardMember& M = g.m[m];
+  backward_tile(M.net, M.rows, M.saved, M.dy, M.dx, M.dz, M.vec_mask, image,
+                (int64_t)((int)blockIdx.x - g.first[m]) * TM);
+}
+
 // ---- backward (ii): every layer's dW and db in one grouped launch ----------------------------
 // A workgroup owns one (32 in, 64 out) tile of one layer's dW = a^T . dz, the
 // sum running over the rows. Its 8 waves each sum one contiguous slice of the
@@ -267,21 +304,20 @@ __global__ void __launch_bounds__(256) mlp_backward_kernel(MlpNet net, int64_t r
 // workgroups of the first in-tile. No floating-point atomics: the order of
 // every sum depends on (rows, shapes) alone.
 
-__global__ void __launch_bounds__(64 * GW) mlp_grad_kernel(MlpNet net, MlpGrads G, int64_t rows,
-                                                           const float* __restrict__ x,
-                                                           int64_t x_stride,
-                                                           const float* __restrict__ saved,
-                                                           const float* __restrict__ dy,
-                                                           const float* __restrict__ dz) {
-  __shared__ float red[GW * 16 * 64];
+// (`block` is the workgroup's index among the network's own)
+__device__ __forceinline__ void grad_tile(const MlpNet& net, const MlpGrads& G, int64_t rows,
+                                          const float* __restrict__ x, int64_t x_stride,
+                                          const float* __restrict__ saved,
+                                          const float* __restrict__ dy,
+                                          const float* __restrict__ dz, float* red, int block) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 31, h = lane >> 5;
   const int L = net.n_layers, kind = net.activation;
   int l = 0;
-  while ((int)blockIdx.x >= G.first[l + 1]) ++l;
+  while (block >= G.first[l + 1]) ++l;
   const int K = net.in[l], N = net.out[l];
   const int n_out_tiles = (N + MLP_GRAD_TILE_OUT - 1) / MLP_GRAD_TILE_OUT;
-  const int tile = (int)blockIdx.x - G.first[l];
+  const int tile = block - G.first[l];
   const int mt = tile / n_out_tiles, nt = tile % n_out_tiles;
   float* __restrict__ dw = G.dw[l];
   float* __restrict__ db = mt == 0 ? G.db[l] : nullptr;
@@ -362,6 +398,25 @@ __global__ void __launch_bounds__(64 * GW) mlp_grad_kernel(MlpNet net, MlpGrads 
   }
 }
 
+__global__ void __launch_bounds__(64 * GW) mlp_grad_kernel(MlpNet net, MlpGrads G, int64_t rows,
+                                                           const float* __restrict__ x,
+                                                           int64_t x_stride,
+                                                           const float* __restrict__ saved,
+                                                           const float* __restrict__ dy,
+                                                           const float* __restrict__ dz) {
+  __shared__ float red[GW * 16 * 64];
+  grad_tile(net, G, rows, x, x_stride, saved, dy, dz, red, (int)blockIdx.x);
+}
+
+__global__ void __launch_bounds__(64 * GW) mlp_group_grad_kernel(MlpGroupGrad g) {
+  __shared__ float red[GW * 16 * 64];
+  int m = 0;
+  while ((int)blockIdx.x >= g.first[m + 1]) ++m;
+  const MlpGradMember& M = g.m[m];
+  grad_tile(M.net, M.grads, M.rows, M.x, M.x_stride, M.saved, M.dy, M.dz, red,
+            (int)blockIdx.x - g.first[m]);
+}
+
 }  // namespace
 
 hipError_t launch_mlp_forward(const MlpNet& net, int64_t rows, const float* x, int64_t x_stride,
@@ -371,34 +426,108 @@ hipError_t launch_mlp_forward(const MlpNet& net, int64_t rows, const float* x, i
   return hipGetLastError();
 }
 
-hipError_t launch_mlp_backward(const MlpNet& net, MlpGrads& G, int64_t rows, const float* x,
-                               int64_t x_stride, const float* saved, const float* dy, float* dx,
-                               float* dz, hipStream_t s) {
+namespace {
+
+// launch (ii)'s plan for one network: G.first, and the workgroups it takes;
+// *hidden_grads when a hidden layer's gradient is wanted (launch (i) must run)
+int plan_grads(const MlpNet& net, MlpGrads& G, bool* hidden_grads) {
   const int L = net.n_layers;
   int total = 0;
-  bool hidden_grads = false;
+  *hidden_grads = false;
   for (int l = 0; l < L; ++l) {
     G.first[l] = total;
     if (!G.dw[l] && !G.db[l]) continue;
-    if (l + 1 < L) hidden_grads = true;
+    if (l + 1 < L) *hidden_grads = true;
     const int in_tiles = G.dw[l] ? (net.in[l] + MLP_GRAD_TILE_IN - 1) / MLP_GRAD_TILE_IN : 1;
     total += in_tiles * ((net.out[l] + MLP_GRAD_TILE_OUT - 1) / MLP_GRAD_TILE_OUT);
   }
   for (int l = L; l <= BX_MLP_MAX_LAYERS; ++l) G.first[l] = total;
+  return total;
+}
+
+// which layers' transposed weight rows take 16-byte loads
+uint32_t vec_layers(const MlpNet& net) {
+  uint32_t vec_mask = 0;
+  for (int l = 0; l < net.n_layers; ++l)
+    if (net.out[l] % 4 == 0 && ((uintptr_t)net.w[l] & 15) == 0) vec_mask |= 1u << l;
+  return vec_mask;
+}
+
+int row_tiles(int64_t rows) { return (int)((rows + TM - 1) / TM); }
+
+}  // namespace
+
+hipError_t launch_mlp_backward(const MlpNet& net, MlpGrads& G, int64_t rows, const float* x,
+                               int64_t x_stride, const float* saved, const float* dy, float* dx,
+                               float* dz, hipStream_t s) {
+  bool hidden_grads = false;
+  const int total = plan_grads(net, G, &hidden_grads);
   if (dx || hidden_grads) {
-    // which layers' transposed weight rows take 16-byte loads
-    uint32_t vec_mask = 0;
-    for (int l = 0; l < L; ++l)
-      if (net.out[l] % 4 == 0 && ((uintptr_t)net.w[l] & 15) == 0) vec_mask |= 1u << l;
-    dim3 grid((unsigned)((rows + TM - 1) / TM));
-    hipLaunchKernelGGL(mlp_backward_kernel, grid, dim3(256), 0, s, net, rows, saved, dy, dx, dz,
-                       vec_mask);
+    hipLaunchKernelGGL(mlp_backward_kernel, dim3((unsigned)row_tiles(rows)), dim3(256), 0, s, net,
+                       rows, saved, dy, dx, dz, vec_layers(net));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   if (total) {
     hipLaunchKernelGGL(mlp_grad_kernel, dim3((unsigned)total), dim3(64 * GW), 0, s, net, G, rows, x,
                        x_stride, saved, dy, dz);
+    return hipGetLastError();
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_mlp_group_forward(const MlpForwardMember* members, int n, hipStream_t s) {
+  MlpGroupForward g{};
+  int total = 0, k = 0;
+  for (int i = 0; i < n; ++i) {
+    if (members[i].rows == 0) continue;
+    g.first[k] = total;
+    g.m[k++] = members[i];
+    total += row_tiles(members[i].rows);
+  }
+  for (int i = k; i <= BX_MLP_MAX_GROUP; ++i) g.first[i] = total;
+  if (!total) return hipSuccess;
+  hipLaunchKernelGGL(mlp_group_forward_kernel, dim3((unsigned)total), dim3(256), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_mlp_group_backward(MlpGradMember* members, float* const* dx, int n,
+                                     hipStream_t s) {
+  MlpGroupBackward b{};
+  MlpGroupGrad g{};
+  int chain_total = 0, grad_total = 0, kb = 0, kg = 0;
+  for (int i = 0; i < n; ++i) {
+    MlpGradMember& M = members[i];
+    if (M.rows == 0 || !M.dy) continue;
+    bool hidden_grads = false;
+    const int tiles = plan_grads(M.net, M.grads, &hidden_grads);
+    if (dx[i] || hidden_grads) {
+      b.first[kb] = chain_total;
+      MlpBackwardMember& B = b.m[kb++];
+      B.net = M.net;
+      B.rows = M.rows;
+      B.saved = M.saved;
+      B.dy = M.dy;
+      B.dx = dx[i];
+      B.dz = const_cast<float*>(M.dz);
+      B.vec_mask = vec_layers(M.net);
+      chain_total += row_tiles(M.rows);
+    }
+    if (tiles) {
+      g.first[kg] = grad_total;
+      g.m[kg++] = M;
+      grad_total += tiles;
+    }
+  }
+  for (int i = kb; i <= BX_MLP_MAX_GROUP; ++i) b.first[i] = chain_total;
+  for (int i = kg; i <= BX_MLP_MAX_GROUP; ++i) g.first[i] = grad_total;
+  if (chain_total) {
+    hipLaunchKernelGGL(mlp_group_backward_kernel, dim3((unsigned)chain_total), dim3(256), 0, s, b);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  if (grad_total) {
+    hipLaunchKernelGGL(mlp_group_grad_kernel, dim3((unsigned)grad_total), dim3(64 * GW), 0, s, g);
     return hipGetLastError();
   }
   return hipSuccess;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/brax_amd.h"
+#include "../../include/brax_amd_mlp_group.h"
 
 namespace bx {
 
@@ -39,6 +40,54 @@ struct MlpGrads {
   int32_t first[BX_MLP_MAX_LAYERS + 1];
 };
 
+// The group launches' member tables, carried in the kernel arguments: each
+// member is a complete problem of its own. `first` is the members' prefix
+// table over the launch's workgroups (the entries past the last member hold
+// the total). A member that takes no part in a launch is not in its table.
+struct MlpForwardMember {
+  MlpNet net;
+  int64_t rows;
+  const float* x;
+  int64_t x_stride;
+  float* y;
+  float* saved;
+};
+struct MlpBackwardMember {
+  MlpNet net;
+  int64_t rows;
+  const float* saved;
+  const float* dy;
+  float* dx;
+  float* dz;
+  uint32_t vec_mask;
+};
+struct MlpGradMember {
+  MlpNet net;
+  MlpGrads grads;
+  int64_t rows;
+  const float* x;
+  int64_t x_stride;
+  const float* saved;
+  const float* dy;
+  const float* dz;
+};
+struct MlpGroupForward {
+  int32_t first[BX_MLP_MAX_GROUP + 1];
+  MlpForwardMember m[BX_MLP_MAX_GROUP];
+};
+struct MlpGroupBackward {
+  int32_t first[BX_MLP_MAX_GROUP + 1];
+  MlpBackwardMember m[BX_MLP_MAX_GROUP];
+};
+struct MlpGroupGrad {
+  int32_t first[BX_MLP_MAX_GROUP + 1];
+  MlpGradMember m[BX_MLP_MAX_GROUP];
+};
+// HIP's limit on a launch's arguments
+static_assert(sizeof(MlpGroupForward) <= 4096, "forward group arguments above 4 KB");
+static_assert(sizeof(MlpGroupBackward) <= 4096, "backward group arguments above 4 KB");
+static_assert(sizeof(MlpGroupGrad) <= 4096, "gradient group arguments above 4 KB");
+
 hipError_t launch_mlp_forward(const MlpNet& net, int64_t rows, const float* x, int64_t x_stride,
                               float* y, float* saved, hipStream_t s);
 // launch (i): the reverse chain (dz of the hidden layers to `dz`, dx when not
@@ -47,5 +96,12 @@ hipError_t launch_mlp_forward(const MlpNet& net, int64_t rows, const float* x, i
 hipError_t launch_mlp_backward(const MlpNet& net, MlpGrads& grads, int64_t rows, const float* x,
                                int64_t x_stride, const float* saved, const float* dy, float* dx,
                                float* dz, hipStream_t s);
+// The same launches for n <= BX_MLP_MAX_GROUP members at once: one forward
+// launch; at most one launch (i) and one launch (ii). A member with rows = 0
+// contributes no workgroups, one with a null dy takes no part in the backward
+// launches; dx[i] is member i's input gradient or null.
+hipError_t launch_mlp_group_forward(const MlpForwardMember* members, int n, hipStream_t s);
+hipError_t launch_mlp_group_backward(MlpGradMember* members, float* const* dx, int n,
+                                     hipStream_t s);
 
 }  // namespace bx

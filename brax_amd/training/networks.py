@@ -60,6 +60,19 @@ def mlp(layers: Layers, x: torch.Tensor, activation: str = 'swish', fused=False)
   return x
 
 
+def mlp_many(members, fused=False, fused_group=False) -> List[torch.Tensor]:
+  """`[mlp(layers, x, activation, fused) for layers, x, activation in members]`
+  for networks evaluated at the same point of a step. `fused_group` other than
+  False gives them shared launches through `fused_mlp.mlp_group` (True: the
+  group kernels or NotImplementedError, also where `fused` is False; None: them
+  where they apply, else the loop)."""
+  if fused_group is not False:
+    from brax_amd.training import fused_mlp  # pylint: disable=import-outside-toplevel
+    if fused_mlp.use_group(fused_group, fused, members):
+      return fused_mlp.apply_group(members)
+  return [mlp(layers, x, activation, fused) for layers, x, activation in members]
+
+
 def parameters(*networks: Layers) -> List[torch.Tensor]:
   return [t for layers in networks for wb in layers for t in wb]
 

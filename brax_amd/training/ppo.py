@@ -85,7 +85,7 @@ class Learner(driver.GradientLearner):
                normalize_observations: bool = False, normalize_advantage: bool = True,
                seed: int = 0, network_factory=ppo_networks.make_ppo_networks, device=None,
                fused_gae: Optional[bool] = None, action_repeat: int = 1, fused_mlp=False,
-               fused_head=False, fused_adam=False):
+               fused_head=False, fused_adam=False, fused_group=False):
     assert batch_size * num_minibatches % num_envs == 0
     self.env, self.device = env, torch.device(device)
     self.action_repeat = int(action_repeat)
@@ -94,7 +94,7 @@ class Learner(driver.GradientLearner):
     self.num_updates_per_batch = int(num_updates_per_batch)
     self.unrolls = batch_size * num_minibatches // num_envs
     self.seed, self.fused_gae, self.fused_mlp = int(seed), fused_gae, fused_mlp
-    self.fused_head, self.fused_adam = fused_head, fused_adam
+    self.fused_head, self.fused_adam, self.fused_group = fused_head, fused_adam, fused_group
     self.loss_kwargs = dict(entropy_cost=entropy_cost, discounting=discounting,
                             reward_scaling=reward_scaling, gae_lambda=gae_lambda,
                             clipping_epsilon=clipping_epsilon,
@@ -151,7 +151,8 @@ class Learner(driver.GradientLearner):
         eps = torch.randn((bs, self.unroll_length, A), generator=self._gen, device=self.device)
         loss, metrics = ppo_loss(self.policy_layers, self.value_layers, self._mean_std, mb, eps,
                                  fused=self.fused_gae, fused_mlp=self.fused_mlp,
-                                 fused_head=self.fused_head, **self.loss_kwargs)
+                                 fused_head=self.fused_head, fused_group=self.fused_group,
+                                 **self.loss_kwargs)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.optimizer.step()
@@ -178,7 +179,8 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
           deterministic_eval: bool = False, network_factory=ppo_networks.make_ppo_networks,
           progress_fn: Callable[[int, dict], None] = lambda *args: None,
           normalize_advantage: bool = True, eval_env=None, device=None,
-          fused_gae: Optional[bool] = None, fused_mlp=False, fused_head=False, fused_adam=False):
+          fused_gae: Optional[bool] = None, fused_mlp=False, fused_head=False, fused_adam=False,
+          fused_group=False):
   """PPO training; the reference's arguments and defaults
   (`ppo/train.py:61-86`).
 
@@ -200,6 +202,9 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
     fused_adam: the optimiser (False: `torch.optim.Adam`; True:
       `optim.FusedAdam`, one launch per Adam step, or NotImplementedError; None:
       `FusedAdam` where it applies).
+    fused_group: `ppo_loss`'s: the loss's three network evaluations share one
+      forward launch, the two networks' backward passes two (off by default; it
+      needs `fused_mlp`).
   Returns:
     `(make_policy, params, metrics)`: `make_policy(params, deterministic=False)`
     gives an `MLPPolicy`; `params` is (the normaliser or None, the policy
@@ -220,7 +225,7 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
                     normalize_advantage=normalize_advantage, seed=seed,
                     network_factory=network_factory, device=dev, fused_gae=fused_gae,
                     action_repeat=action_repeat, fused_mlp=fused_mlp, fused_head=fused_head,
-                    fused_adam=fused_adam)
+                    fused_adam=fused_adam, fused_group=fused_group)
   # jax.random.PRNGKey(seed) layout; the evaluator's key is the split's other half
   learner.reset(wrappers.split_key(np.array([0, int(seed)], np.uint32))[0])
   eval_policy = learner.make_policy(deterministic=True) if deterministic_eval else learner.actor

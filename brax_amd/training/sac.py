@@ -124,20 +124,20 @@ def _apply(optimizer, params, grads):
 
 
 def _chained_gradients(ts: TrainingState, normalizer, transitions, eps, reward_scaling, discounting,
-                       fused_mlp):
+                       fused_mlp, fused_group=False):
   """The three losses as torch expressions (`sac_losses`) and autograd's
   gradients of them: `(a_grads, c_grads, p_grads, metrics)`."""
   eps_alpha, eps_critic, eps_actor = eps
   policy_params = parameters(ts.policy_layers)
   q_params = sac_networks.q_parameters(ts.q_layers)
   a_loss = sac_losses.alpha_loss(ts.log_alpha, ts.policy_layers, normalizer, transitions, eps_alpha,
-                                 fused_mlp)
+                                 fused_mlp, fused_group)
   alpha = torch.exp(ts.log_alpha.detach())
   c_loss = sac_losses.critic_loss(ts.q_layers, ts.policy_layers, normalizer, ts.target_q_layers,
                                   alpha, transitions, eps_critic, reward_scaling, discounting,
-                                  fused_mlp)
+                                  fused_mlp, fused_group)
   p_loss = sac_losses.actor_loss(ts.policy_layers, normalizer, ts.q_layers, alpha, transitions,
-                                 eps_actor, fused_mlp)
+                                 eps_actor, fused_mlp, fused_group)
   a_grads = torch.autograd.grad(a_loss, [ts.log_alpha])
   c_grads = torch.autograd.grad(c_loss, q_params)
   p_grads = torch.autograd.grad(p_loss, policy_params)
@@ -145,17 +145,20 @@ def _chained_gradients(ts: TrainingState, normalizer, transitions, eps, reward_s
                                      'alpha_loss': a_loss.detach()}
 
 
-def _gradients(ts, normalizer, transitions, eps, reward_scaling, discounting, fused_mlp, fused_head):
+def _gradients(ts, normalizer, transitions, eps, reward_scaling, discounting, fused_mlp, fused_head,
+               fused_group=False):
   if use_kernel(fused_head, 'sac head',
                 lambda: sac_head.fused_supported(ts, normalizer, transitions, eps)):
     return sac_head.gradients(ts, normalizer, transitions, eps, reward_scaling, discounting,
-                              fused_mlp)
-  return _chained_gradients(ts, normalizer, transitions, eps, reward_scaling, discounting, fused_mlp)
+                              fused_mlp, fused_group)
+  return _chained_gradients(ts, normalizer, transitions, eps, reward_scaling, discounting, fused_mlp,
+                            fused_group)
 
 
 def sgd_step(ts: TrainingState, normalizer, transitions: Mapping[str, torch.Tensor],
              eps: Tuple[torch.Tensor, torch.Tensor, torch.Tensor], reward_scaling: float = 1.0,
-             discounting: float = 0.9, tau: float = 0.005, fused_mlp=False, fused_head=False):
+             discounting: float = 0.9, tau: float = 0.005, fused_mlp=False, fused_head=False,
+             fused_group=False):
   """One gradient step in the reference's order (`train.py:214-269`).
 
   The alpha update comes first, but the critic and actor losses read `exp` of
@@ -177,6 +180,10 @@ def sgd_step(ts: TrainingState, normalizer, transitions: Mapping[str, torch.Tens
     fused_head: how the three gradients are taken (False: `sac_losses` and
       autograd; True: `sac_head.gradients`, four launches between the networks,
       or NotImplementedError; None: that where it applies).
+    fused_group: networks evaluated at the same point of the step share
+      launches (`networks.mlp_many`): with the head the critics' twelve launches
+      become three, without it each `q_apply` groups its critics. It needs the
+      MLP kernels: with `fused_mlp=False`, True raises and None falls back.
   Returns:
     the metrics (detached tensors): critic_loss, actor_loss, alpha_loss, alpha;
     from the kernels a `sac_head.Metrics`, whose `vector` is the three losses.
@@ -186,7 +193,7 @@ def sgd_step(ts: TrainingState, normalizer, transitions: Mapping[str, torch.Tens
   policy_params = parameters(ts.policy_layers)
   q_params = sac_networks.q_parameters(ts.q_layers)
   a_grads, c_grads, p_grads, metrics = _gradients(ts, normalizer, transitions, eps, reward_scaling,
-                                                  discounting, fused_mlp, fused_head)
+                                                  discounting, fused_mlp, fused_head, fused_group)
   if ts.fused_optimizer is not None:
     ts.fused_optimizer.step(grads=[*a_grads, *c_grads, *p_grads])
   else:
@@ -214,7 +221,7 @@ class Learner(driver.GradientLearner):
                tau: float = 0.005, normalize_observations: bool = False, seed: int = 0,
                network_factory=sac_networks.make_sac_networks, device=None,
                action_repeat: int = 1, fused_buffer: Optional[bool] = None, fused_mlp=False,
-               fused_adam=False, fused_head=False):
+               fused_adam=False, fused_head=False, fused_group=False):
     self.env, self.device = env, torch.device(device)
     self.num_envs, self.action_repeat = int(num_envs), int(action_repeat)
     self.batch_size, self.grad_updates_per_step = int(batch_size), int(grad_updates_per_step)
@@ -222,7 +229,7 @@ class Learner(driver.GradientLearner):
     self.seed, self.fused_buffer, self.fused_mlp = int(seed), fused_buffer, fused_mlp
     self.loss_kwargs = dict(reward_scaling=reward_scaling, discounting=discounting, tau=tau)
     O, A = env.observation_size, env.action_size
-    self.fused_adam, self.fused_head = fused_adam, fused_head
+    self.fused_adam, self.fused_head, self.fused_group = fused_adam, fused_head, fused_group
     self.ts = init_training_state(O, A, learning_rate, network_factory, seed, self.device,
                                   fused_adam=fused_adam, tau=tau)
     self.normalizer = RunningStatistics(O, self.device) if normalize_observations else None
@@ -271,7 +278,8 @@ class Learner(driver.GradientLearner):
       eps = tuple(torch.randn((self.batch_size, A), generator=self._gen, device=self.device)
                   for _ in range(3))
       metrics = sgd_step(self.ts, self._mean_std, mb, eps, fused_mlp=self.fused_mlp,
-                         fused_head=self.fused_head, **self.loss_kwargs)
+                         fused_head=self.fused_head, fused_group=self.fused_group,
+                         **self.loss_kwargs)
       # (the fused head's three losses in one addition, alpha in another)
       driver.add_metrics(sums, metrics)
     self.actor.load_(detached(self.ts.policy_layers))
@@ -296,7 +304,7 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
           progress_fn: Callable[[int, dict], None] = lambda *args: None,
           checkpoint_logdir: Optional[str] = None, eval_env=None, device=None,
           fused_buffer: Optional[bool] = None, fused_mlp=False, fused_adam=False,
-          fused_head=False):
+          fused_head=False, fused_group=False):
   """SAC training; the reference's arguments and defaults
   (`sac/train.py:106-129`).
 
@@ -324,6 +332,8 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
     fused_head: the three losses and their gradients between the networks
       (False: `sac_losses` and autograd; True: `sac_head.gradients`, four
       launches, or NotImplementedError; None: that where it applies).
+    fused_group: `sgd_step`'s: the critics evaluated at the same point of a
+      gradient step share launches (off by default; it needs `fused_mlp`).
   Returns:
     `(make_policy, params, metrics)`: `make_policy(params, deterministic=False)`
     gives an `MLPPolicy`; `params` is (the normaliser or None, the policy
@@ -348,7 +358,7 @@ def train(environment, num_timesteps: int, episode_length: int, action_repeat: i
                     normalize_observations=normalize_observations, seed=seed,
                     network_factory=network_factory, device=dev, action_repeat=action_repeat,
                     fused_buffer=fused_buffer, fused_mlp=fused_mlp, fused_adam=fused_adam,
-                    fused_head=fused_head)
+                    fused_head=fused_head, fused_group=fused_group)
   # jax.random.PRNGKey(seed) layout; the evaluator's key is the split's other half
   learner.reset(wrappers.split_key(np.array([0, int(seed)], np.uint32))[0])
   eval_policy = learner.make_policy(deterministic=True) if deterministic_eval else learner.actor

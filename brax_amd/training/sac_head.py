@@ -22,6 +22,9 @@ three gradients over `bx_sac_head_*` (`include/brax_amd.h`):
 8. the policy's backward pass.
 
 The networks go through `networks.mlp(..., fused_mlp)` as in the chained form.
+With `fused_group` step 4's six critic evaluations are one forward launch and
+step 6's four backward passes two (`fused_mlp.group_forward` /
+`group_backward`): each member's bits are the ungrouped call's.
 """
 import ctypes as C
 from typing import Optional
@@ -30,6 +33,7 @@ import torch
 
 from brax_amd import _native, abi
 from brax_amd.system import launch
+from brax_amd.training import fused_mlp as fused_mlp_lib
 from brax_amd.training import sac_losses
 from brax_amd.training.networks import detached, mlp, parameters
 from brax_amd.training.sac_networks import ACTIVATION
@@ -207,7 +211,7 @@ def _unit_rows(t):
 
 
 def gradients(ts, normalizer, transitions, eps, reward_scaling: float = 1.0,
-              discounting: float = 0.9, fused_mlp=False):
+              discounting: float = 0.9, fused_mlp=False, fused_group=False):
   """The three gradients of one SAC step through the kernels.
 
   Args as `sac.sgd_step`'s; the tensors must pass `fused_supported`.
@@ -238,20 +242,39 @@ def gradients(ts, normalizer, transitions, eps, reward_scaling: float = 1.0,
   sample_call([(lg, eps_alpha, None, buf['log_probs'][0]),
                (_unit_rows(next_logits), eps_critic, x_next[:, O:], buf['log_probs'][1]),
                (lg, eps_actor, buf['x_pi'][:, O:], buf['log_probs'][2])])
-  q_old = [mlp(c, x_cur, ACTIVATION, fused_mlp) for c in ts.q_layers]
-  with torch.no_grad():
-    next_q = [mlp(c, x_next, ACTIVATION, fused_mlp) for c in ts.target_q_layers]
-  q_pi = [mlp(detached(c), x_pi, ACTIVATION, fused_mlp) for c in ts.q_layers]
+  # the critics' evaluations: Q on X_cur, Qtarget on X_next, Q on X_pi
+  evals = [(c, x) for cs, x in ((ts.q_layers, x_cur), (ts.target_q_layers, x_next),
+                                (ts.q_layers, buf['x_pi'])) for c in cs]
+  group = fused_mlp_lib.use_group(fused_group, fused_mlp, evals, ACTIVATION)
+  if group:
+    members = [(parameters(detached(c)), x, ACTIVATION) for c, x in evals]
+    ys, saveds = fused_mlp_lib.group_forward(members, [True] * n + [False] * n + [True] * n)
+    q_old, next_q, q_pi = ys[:n], ys[n:2 * n], ys[2 * n:]
+  else:
+    q_old = [mlp(c, x_cur, ACTIVATION, fused_mlp) for c in ts.q_layers]
+    with torch.no_grad():
+      next_q = [mlp(c, x_next, ACTIVATION, fused_mlp) for c in ts.target_q_layers]
+    q_pi = [mlp(detached(c), x_pi, ACTIVATION, fused_mlp) for c in ts.q_layers]
   flat = lambda ts_: [t.detach().contiguous() for t in ts_]  # noqa: E731
   losses_call(buf['log_probs'], flat(q_old), flat(next_q), flat(q_pi), transitions['reward'],
               transitions['discount'], transitions['truncation'], ts.log_alpha.detach(),
               reward_scaling, discounting, sac_losses.target_entropy(A), buf['dq_old'],
               buf['dq_pi'], buf['g_lp'], buf['workspace'])
   c_grads = []
-  for c, q in zip(range(n), q_old):
-    c_grads += torch.autograd.grad(q, parameters(ts.q_layers[c]), grad_outputs=buf['dq_old'][c])
-  dx = [_unit_rows(torch.autograd.grad(q, x_pi, grad_outputs=buf['dq_pi'][c])[0])
-        for c, q in enumerate(q_pi)]
+  if group:
+    # dW / db from X_cur and dx from X_pi; the target critics take no part
+    on = members[:n] + members[2 * n:]
+    dxs, grads = fused_mlp_lib.group_backward(
+        on, saveds[:n] + saveds[2 * n:], buf['dq_old'] + buf['dq_pi'], [False] * n + [True] * n,
+        [[True] * len(m[0]) for m in on[:n]] + [[False] * len(m[0]) for m in on[n:]])
+    for g in grads[:n]:
+      c_grads += g
+    dx = dxs[n:]
+  else:
+    for c, q in zip(range(n), q_old):
+      c_grads += torch.autograd.grad(q, parameters(ts.q_layers[c]), grad_outputs=buf['dq_old'][c])
+    dx = [_unit_rows(torch.autograd.grad(q, x_pi, grad_outputs=buf['dq_pi'][c])[0])
+          for c, q in enumerate(q_pi)]
   sample_backward_call(lg, eps_actor, buf['g_lp'], [d[:, O:] for d in dx], buf['dlogits'], losses,
                        dlog_alpha, buf['workspace'])
   p_grads = torch.autograd.grad(logits, policy_params, grad_outputs=buf['dlogits'])

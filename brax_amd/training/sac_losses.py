@@ -37,8 +37,10 @@ def _sample(policy_layers, obs, eps, fused_mlp=False):
 
 def alpha_loss(log_alpha: torch.Tensor, policy_layers: Layers, normalizer,
                transitions: Mapping[str, torch.Tensor], eps: torch.Tensor,
-               fused_mlp=False) -> torch.Tensor:
-  """Eq 18 of arXiv:1812.05905 (`losses.py:40-51`); differentiable in `log_alpha`."""
+               fused_mlp=False, fused_group=False) -> torch.Tensor:
+  """Eq 18 of arXiv:1812.05905 (`losses.py:40-51`); differentiable in `log_alpha`.
+  (`fused_group` has nothing to group here: one network.)"""
+  del fused_group
   action_size = eps.shape[-1]
   _, log_prob = _sample(policy_layers, normalize(transitions['observation'], normalizer), eps,
                         fused_mlp)
@@ -51,14 +53,15 @@ def critic_loss(q_layers: List[Layers], policy_layers: Layers, normalizer,
                 target_q_layers: List[Layers], alpha: torch.Tensor,
                 transitions: Mapping[str, torch.Tensor], eps: torch.Tensor,
                 reward_scaling: float = 1.0, discounting: float = 0.9,
-                fused_mlp=False) -> torch.Tensor:
-  """`losses.py:53-79`; differentiable in `q_layers` (the target is held)."""
+                fused_mlp=False, fused_group=False) -> torch.Tensor:
+  """`losses.py:53-79`; differentiable in `q_layers` (the target is held).
+  `fused_group`: each `q_apply`'s critics share their launches."""
   obs = normalize(transitions['observation'], normalizer)
   next_obs = normalize(transitions['next_observation'], normalizer)
-  q_old_action = q_apply(q_layers, obs, transitions['action'], fused_mlp)
+  q_old_action = q_apply(q_layers, obs, transitions['action'], fused_mlp, fused_group)
   next_raw, next_log_prob = _sample(policy_layers, next_obs, eps, fused_mlp)
   next_action = torch.tanh(next_raw)
-  next_q = q_apply(target_q_layers, next_obs, next_action, fused_mlp)
+  next_q = q_apply(target_q_layers, next_obs, next_action, fused_mlp, fused_group)
   next_v = torch.min(next_q, dim=-1).values - alpha * next_log_prob
   target_q = (_scalar(transitions['reward']) * reward_scaling
               + _scalar(transitions['discount']) * discounting * next_v).detach()
@@ -70,11 +73,12 @@ def critic_loss(q_layers: List[Layers], policy_layers: Layers, normalizer,
 
 def actor_loss(policy_layers: Layers, normalizer, q_layers: List[Layers], alpha: torch.Tensor,
                transitions: Mapping[str, torch.Tensor], eps: torch.Tensor,
-               fused_mlp=False) -> torch.Tensor:
-  """`losses.py:81-94`; differentiable in `policy_layers`."""
+               fused_mlp=False, fused_group=False) -> torch.Tensor:
+  """`losses.py:81-94`; differentiable in `policy_layers`. `fused_group` as
+  `critic_loss`'s."""
   obs = normalize(transitions['observation'], normalizer)
   raw, log_prob = _sample(policy_layers, obs, eps, fused_mlp)
   action = torch.tanh(raw)
-  q_action = q_apply(q_layers, obs, action, fused_mlp)
+  q_action = q_apply(q_layers, obs, action, fused_mlp, fused_group)
   min_q = torch.min(q_action, dim=-1).values
   return torch.mean(alpha * log_prob - min_q)

@@ -11,7 +11,7 @@ from typing import List, Sequence, Tuple
 
 import torch
 
-from brax_amd.training.networks import Layers, make_layers, mlp
+from brax_amd.training.networks import Layers, make_layers, mlp_many
 
 ACTIVATION = 'relu'
 
@@ -28,10 +28,13 @@ def make_sac_networks(observation_size: int, action_size: int,
 
 
 def q_apply(q_layers: List[Layers], obs: torch.Tensor, action: torch.Tensor,
-            fused_mlp=False) -> torch.Tensor:
-  """`QModule.__call__` on observations that are already normalised: (B, n_critics)."""
+            fused_mlp=False, fused_group=False) -> torch.Tensor:
+  """`QModule.__call__` on observations that are already normalised: (B,
+  n_critics). With `fused_group` the critics share their launches
+  (`networks.mlp_many`)."""
   hidden = torch.cat([obs, action], dim=-1)
-  return torch.cat([mlp(c, hidden, ACTIVATION, fused_mlp) for c in q_layers], dim=-1)
+  return torch.cat(mlp_many([(c, hidden, ACTIVATION) for c in q_layers], fused_mlp, fused_group),
+                   dim=-1)
 
 
 def q_parameters(q_layers: List[Layers]) -> List[torch.Tensor]:

@@ -15,12 +15,20 @@
             alternating on one learner, `--steps` steps each.
   sac       the gradient updates of one Ant SAC step (`tools/sac_bench.py`'s
             setting: 4,096 envs, batch 256, 64 updates, (256, 256)), likewise.
+  `--group` measures the group launches instead (`fused_mlp.mlp_group`: several
+  networks in one forward and two backward launches) against the same members
+  through `fused_mlp` one by one (the single entry points), both under
+  autograd as the learners run them, alternating, with their launch counts: the SAC critic group (six evaluations of 95 -> 256 -> 256 -> 1 at
+  256 rows forward, four of them backward: dW / db for two, dx for two) and
+  the PPO group (policy at 5,120 rows, value at 6,144, bootstrap value at
+  1,024 forward; policy and value backward).
   `--parent` runs ppo and sac without naming `fused_mlp` at all, so the same
   file measures a tree from before the keyword existed.
 
 Prints one JSON line per measurement.
 
     python tools/mlp_bench.py [--parts mlp,launches,ppo,sac] [--runs 7] [--calls 100] [--steps 3]
+    python tools/mlp_bench.py --group [--runs 7] [--calls 100]
 """
 import functools
 
@@ -132,9 +140,77 @@ def bench_sac(dev, steps, parent):
   emit(res)
 
 
+# a group: (name, activation, networks {name: sizes}, members (network, x, rows, backward)):
+# backward is None (forward only), 'params' (dW / db) or 'dx'
+GROUPS = (
+    ('sac critics', 'relu', {'q1': (95, 256, 256, 1), 'q2': (95, 256, 256, 1),
+                             't1': (95, 256, 256, 1), 't2': (95, 256, 256, 1)},
+     (('q1', 'cur', 256, 'params'), ('q2', 'cur', 256, 'params'), ('t1', 'next', 256, None),
+      ('t2', 'next', 256, None), ('q1', 'pi', 256, 'dx'), ('q2', 'pi', 256, 'dx'))),
+    ('ppo', 'swish', {'policy': (87,) + (32,) * 4 + (16,), 'value': (87,) + (256,) * 5 + (1,)},
+     (('policy', 'obs5120', 5120, 'params'), ('value', 'obs6144', 6144, 'params'),
+      ('value', 'boot', 1024, None))),
+)
+
+
+def _group_forms(activation, nets, members, dev):
+  """Both forms as the learners run them, through autograd: `mlp_group` and one
+  `autograd.grad` for the group, against `fused_mlp` (`bx_mlp_forward` /
+  `bx_mlp_backward`) and one `autograd.grad` per member."""
+  from brax_amd.training import fused_mlp, networks  # pylint: disable=import-outside-toplevel
+  g = torch.Generator().manual_seed(len(members))
+  layers = {k: networks.make_layers(s, g, device=dev) for k, s in nets.items()}
+  xs, table, dys, leaves = {}, [], [], []
+  for net, x, rows, backward in members:
+    key = (x, net if backward == 'dx' else None)  # a leaf of its own per dx: no sum
+    if key not in xs:
+      xs[key] = torch.randn((rows, nets[net][0]), generator=g).to(dev).requires_grad_(backward == 'dx')
+    # (only what a member's backward pass is for requires a gradient)
+    own = layers[net] if backward == 'params' else networks.detached(layers[net])
+    table.append((own, xs[key], activation))
+    dys.append(torch.randn((rows, nets[net][-1]), generator=g).to(dev))
+    leaves.append(networks.parameters(own) if backward == 'params' else
+                  [xs[key]] if backward == 'dx' else [])
+  back = [k for k, m in enumerate(members) if m[3]]
+
+  def grouped():
+    ys = fused_mlp.mlp_group(table, fused=True)
+    return torch.autograd.grad([ys[k] for k in back], [t for k in back for t in leaves[k]],
+                               grad_outputs=[dys[k] for k in back])
+
+  def singly():
+    out = []
+    for k, (own, x, act) in enumerate(table):
+      y = fused_mlp.fused_mlp(own, x, act, fused=True)
+      if leaves[k]:
+        out.append(torch.autograd.grad(y, leaves[k], grad_outputs=dys[k]))
+    return out
+  return {'grouped': grouped, 'singly': singly}
+
+
+def bench_groups(dev, runs, calls):
+  for name, activation, nets, members in GROUPS:
+    forms = _group_forms(activation, nets, members, dev)
+    res = {'measure': 'mlp_group_forward_backward', 'group': name,
+           'members': [list(m) for m in members], 'unit': 'us per iteration', 'runs': runs,
+           'calls_per_region': calls}
+    times = alternate(forms, runs, calls, dev)
+    res.update({k: spread(v, 1e6) for k, v in times.items()})
+    res['singly_over_grouped'] = round(res['singly']['median'] / res['grouped']['median'], 2)
+    for form, fn in forms.items():
+      kernels = [e for e in device_kernels(fn, dev, repeat=4) if 'mlp_' in e.name]
+      res[form + '_launches'] = len(kernels) / 4
+      res[form + '_device_us'] = round(sum(e.device_time for e in kernels) / 4, 1)
+    emit(res)
+
+
 def main():
-  a, dev = start('mlp_bench', tool_args(__doc__, runs=7, calls=100, steps=3,
-                                        parts='mlp,launches,ppo,sac'))
+  ap = tool_args(__doc__, runs=7, calls=100, steps=3, parts='mlp,launches,ppo,sac')
+  ap.add_argument('--group', action='store_true', help='the group launches against single ones')
+  a, dev = start('mlp_bench', ap)
+  if a.group:
+    bench_groups(dev, a.runs, a.calls)
+    return
   parts = parts_of(a, in_parent=('ppo', 'sac'))
   if 'mlp' in parts:
     bench_mlp(dev, a.runs, a.calls)

@@ -12,12 +12,17 @@
       batch, normalised observations), split into unroll, normaliser and
       updates, each ending in a synchronise; the update phase with fused and
       with chained GAE, alternating, median (min .. max) of `--steps` steps.
+  `--group`: only the update phase of such a step with every switch on
+      (`fused_mlp`, `fused_head`, `fused_adam`), `fused_group` on and off on
+      one learner, alternating; with `--parent` the same learner with
+      `fused_group` not named (a tree from before the keyword).
   `--learn`: a longer `inverted_pendulum` run, its evaluation reward after
       every epoch.
 
 Prints one JSON line per measurement.
 
     python tools/ppo_bench.py [--runs 7] [--calls 200] [--steps 3] [--learn]
+    python tools/ppo_bench.py --group [--parent] [--steps 7]
 """
 import time
 
@@ -78,6 +83,35 @@ def bench_step(dev, steps):
   emit(res)
 
 
+def bench_group(dev, steps, parent):
+  learner = ppo_learner(dev, fused_mlp=True, fused_head=True, fused_adam=True)
+  forms = {'parent': None} if parent else {'grouped': True, 'ungrouped': False}
+
+  def update(form):
+    if not parent:
+      learner.fused_group = forms[form]
+    data = learner.collect()
+    learner.update_normalizer(data)
+    t, metrics = timed(lambda: learner.update(data), dev)
+    return t, float(metrics['total_loss'])
+  for form in forms:
+    update(form)  # warm-up: code objects, the allocator, Adam's state
+  rec = {form: [] for form in forms}
+  for _ in range(steps):
+    for form in forms:
+      rec[form].append(update(form))
+  n = ANT_PPO['num_updates_per_batch'] * ANT_PPO['num_minibatches']
+  res = {'measure': 'ppo_update_phase_grouped', 'env': 'ant', **ANT_PPO, 'fused_mlp': True,
+         'fused_head': True, 'fused_adam': True, 'unit': 'ms', 'steps': steps, 'adam_steps': n}
+  for form in forms:
+    res[form] = spread([t for t, _ in rec[form]], 1e3)
+    res[form + '_ms_per_adam_step'] = round(res[form]['median'] / n, 3)
+    res[form + '_last_total_loss'] = rec[form][-1][1]
+  if not parent:
+    res['ungrouped_over_grouped'] = round(res['ungrouped']['median'] / res['grouped']['median'], 3)
+  emit(res)
+
+
 def learn(dev, num_timesteps, num_evals):
   from brax_amd.training import ppo  # pylint: disable=import-outside-toplevel
   curve = []
@@ -104,7 +138,12 @@ def main():
   ap.add_argument('--learn-timesteps', type=int, default=2_000_000)
   ap.add_argument('--learn-evals', type=int, default=6)
   ap.add_argument('--skip-step', action='store_true')
+  ap.add_argument('--group', action='store_true', help='the update phase, fused_group on and off')
+  ap.add_argument('--parent', action='store_true', help='with --group: fused_group not named')
   a, dev = start('ppo_bench', ap)
+  if a.group:
+    bench_group(dev, a.steps, a.parent)
+    return
   for T, B in ((5, 1024), (5, 32768)):
     bench_gae(dev, T, B, a.runs, a.calls)
   if not a.skip_step:

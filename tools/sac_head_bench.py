@@ -13,13 +13,17 @@
   split     one such update phase of each form under `torch.profiler`: the
             kernels' count and device time by owner per gradient step, and the
             names of what is left under 'other torch' in the fused form.
+  group     the same 64 updates with every switch on (`fused_mlp`, `fused_adam`,
+            `fused_head`), `fused_group` on and off on two learners,
+            alternating; with `--parent` one learner with the three older
+            switches on and `fused_group` not named.
   `--parent` runs sac without naming `fused_head` at all, so the same file
   measures a tree from before the keyword existed; `--root` names the tree
   whose package is imported (default: this file's).
 
 Prints one JSON line per measurement.
 
-    python tools/sac_head_bench.py [--parts head,sac,split] [--runs 7] [--calls 50]
+    python tools/sac_head_bench.py [--parts head,sac,split,group] [--runs 7] [--calls 50]
 """
 import collections
 
@@ -59,19 +63,23 @@ def bench_head(dev, runs, calls):
             'all': all_kernels(kernels, 4)})
 
 
-def _learners(dev, parent):
+HEAD_FORMS = {'fused_head': dict(fused_head=True), 'chained_head': dict(fused_head=False)}
+GROUP_FORMS = {'grouped': dict(fused_head=True, fused_group=True),
+               'ungrouped': dict(fused_head=True, fused_group=False)}
+
+
+def _learners(dev, parent, forms=None, parent_form=None):
   """(this tool alone sets the learning rate, the discount and the reward
   scale of the README's SAC run; the others leave `sac.Learner`'s defaults)"""
   env = ant_env(dev, SAC_ANT['num_envs'])
-  forms = {'parent': {}} if parent else {'fused_head': dict(fused_head=True),
-                                         'chained_head': dict(fused_head=False)}
+  forms = {'parent': parent_form or {}} if parent else (forms or HEAD_FORMS)
   return {form: sac_learner(dev, env, learning_rate=6e-4, discounting=0.997, reward_scaling=30.0,
                             fused_mlp=True, fused_adam=True, **kw)
           for form, kw in forms.items()}
 
 
-def bench_sac(dev, steps, parent):
-  learners = _learners(dev, parent)
+def bench_sac(dev, steps, parent, forms=None, parent_form=None, measure='sac_gradient_updates'):
+  learners = _learners(dev, parent, forms, parent_form)
 
   def update(form):
     L = learners[form]
@@ -85,14 +93,16 @@ def bench_sac(dev, steps, parent):
   for _ in range(steps):
     for form in learners:
       rec[form].append(update(form))
-  res = {'measure': 'sac_gradient_updates', 'env': 'ant', **SAC_ANT, 'hidden': [256, 256],
+  res = {'measure': measure, 'env': 'ant', **SAC_ANT, 'hidden': [256, 256],
          'fused_mlp': True, 'fused_adam': True, 'unit': 'ms', 'steps': steps}
   for form in learners:
     res[form] = spread([t for t, _ in rec[form]], 1e3)
     res[form + '_ms_per_update'] = round(res[form]['median'] / SAC_ANT['updates'], 3)
     res[form + '_last_critic_loss'] = rec[form][-1][1]
   if not parent:
-    res['chained_over_fused'] = round(res['chained_head']['median'] / res['fused_head']['median'], 2)
+    fast, slow = list(learners)
+    name = 'chained_over_fused' if forms is None else f'{slow}_over_{fast}'
+    res[name] = round(res[slow]['median'] / res[fast]['median'], 2)
   emit(res)
 
 
@@ -119,13 +129,16 @@ def split_updates(dev):
 def main():
   a, dev = start('sac_head_bench', tool_args(__doc__, runs=7, calls=50, steps=5,
                                              parts='head,sac,split'))
-  parts = parts_of(a, in_parent=('sac',))
+  parts = parts_of(a, in_parent=('sac', 'group'))
   if 'head' in parts:
     bench_head(dev, a.runs, a.calls)
   if 'sac' in parts:
     bench_sac(dev, a.steps, a.parent)
   if 'split' in parts:
     split_updates(dev)
+  if 'group' in parts:
+    bench_sac(dev, a.steps, a.parent, GROUP_FORMS, dict(fused_head=True),
+              'sac_gradient_updates_grouped')
 
 
 if __name__ == '__main__':
